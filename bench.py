@@ -1,8 +1,16 @@
 """Flagship training benchmark — GPT-2.6B (BASELINE.md headline config).
 
 Driver contract:
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 (N>1 launched via torch.distributed.run, one rank per GPU over RCCL.)
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print one JSON result line.  ``--dump-outputs DIR`` additionally
+writes what the last timed step produced (see _dump_outputs) so two builds
+can be compared output for output; inputs and initial weights are seeded and
+identical from run to run.  ``--full`` is where any extra measurement beyond
+the headline (baselines, other precisions/sizes, per-kernel figures) belongs;
+today the benchmark has none, so it changes nothing.
 
 Measures Alpa's headline metric on Alpa's headline config: model TFLOPS for
 GPT-2.6B (H=2560, L=32, heads=32, vocab 51200, seq 1024), batch 32 per GPU,
@@ -66,7 +74,16 @@ def parse_args():
                         "linear fwd+bwd (ops/fp8.py).  NOT the headline "
                         "metric: BASELINE requires bf16 compute; this "
                         "reports dtype=bf16+fp8gemm for comparison")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write the outputs of the "
+                        "last timed step (loss + a seeded sample of the "
+                        "updated parameters) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline "
+                        "figure (none today: the plain run is already just "
+                        "setup + warmup + timed steps)")
     args = p.parse_args()
+    assert args.steps >= 1, "--steps must be >= 1"
     if args.nmb == 0:
         args.nmb = 1
     return args
@@ -81,6 +98,37 @@ def _enable_tunableop():
         os.environ.setdefault("PYTORCH_TUNABLEOP_ENABLED", "1")
         os.environ.setdefault("PYTORCH_TUNABLEOP_TUNING", "0")
         os.environ.setdefault("PYTORCH_TUNABLEOP_FILENAME", base)
+
+
+#: per-parameter sample size for --dump-outputs (GPT-2.6B: ~390 tensors
+#: x 16384 x 4 B = ~26 MB, well under the 64 MB cap)
+_DUMP_SAMPLE = 16384
+_DUMP_MAX_BYTES = 64 * 2**20
+
+
+def _dump_outputs(out_dir: str, loss: torch.Tensor, model) -> None:
+    """Write what a caller of the timed step receives from its last call:
+    the returned loss, and the parameters the step updated in place.  The
+    parameters are too large to dump whole, so each tensor contributes a
+    fixed, seeded sample of its elements (all of them when it is small),
+    concatenated in named_parameters() order.  Everything is float32."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().cpu().numpy().reshape(1))
+    g = torch.Generator().manual_seed(97531)
+    params = list(model.named_parameters())
+    per = min(_DUMP_SAMPLE,
+              max(1, (_DUMP_MAX_BYTES - 4) // (4 * max(len(params), 1))))
+    chunks = []
+    for _, p in params:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > per:
+            idx = torch.randint(0, flat.numel(), (per,), generator=g)
+            flat = flat[idx.to(flat.device)]
+        chunks.append(flat.float().cpu())
+    sample = torch.cat(chunks) if chunks else torch.zeros(0)
+    np.save(os.path.join(out_dir, "params_sample.npy"), sample.numpy())
 
 
 def main():
@@ -215,6 +263,9 @@ def main():
         et_d = et.to(dev) if on_gpu else et
         dist.all_reduce(et_d, op=dist.ReduceOp.MAX)
         elapsed = float(et_d.item())
+
+    if args.dump_outputs and aa.rank() == 0:
+        _dump_outputs(args.dump_outputs, loss, state.model)
 
     ms_per_step = elapsed / args.steps * 1000
     global_batch = batch_per_gpu * dp

@@ -1,5 +1,5 @@
 import sys, time, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, ".")
 def t(fn, it=30):
     for _ in range(5): fn()
     torch.cuda.synchronize(); t0 = time.perf_counter()

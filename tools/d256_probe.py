@@ -1,5 +1,5 @@
 import sys, time, math, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, ".")
 from alpa_amd.ops._backend import hip_ops
 ext = hip_ops()
 def t(fn, it=20):
