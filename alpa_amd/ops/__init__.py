@@ -282,6 +282,14 @@ def flash_attention_varlen(q: torch.Tensor, k: torch.Tensor,
     return o
 
 
+def _qkv_views(qkv: torch.Tensor, num_heads: int):
+    """The q, k, v [B,h,S,d] strided views of a packed [B,S,h*3*d] tensor
+    (per-head [q|k|v] layout); no copies."""
+    B, S, F = qkv.shape
+    qkv5 = qkv.view(B, S, num_heads, 3, F // (3 * num_heads))
+    return tuple(qkv5[:, :, :, i].permute(0, 2, 1, 3) for i in range(3))
+
+
 class _FlashAttentionQKV(torch.autograd.Function):
     """Packed-qkv attention: input [B, S, h*3d] (per-head [q|k|v] layout),
     output [B, S, h*d].  The strided gfx950 kernel reads/writes these
@@ -294,10 +302,7 @@ class _FlashAttentionQKV(torch.autograd.Function):
         d = F // (3 * h)
         if scale is None:
             scale = 1.0 / math.sqrt(d)
-        qkv5 = qkv.view(B, S, h, 3, d)
-        q = qkv5[:, :, :, 0].permute(0, 2, 1, 3)  # [B,h,S,d] strided view
-        k = qkv5[:, :, :, 1].permute(0, 2, 1, 3)
-        v = qkv5[:, :, :, 2].permute(0, 2, 1, 3)
+        q, k, v = _qkv_views(qkv, h)
         if use_hip(qkv):
             o_buf = torch.empty(B, S, h * d, dtype=qkv.dtype,
                                 device=qkv.device)
@@ -319,28 +324,22 @@ class _FlashAttentionQKV(torch.autograd.Function):
         h, causal, scale = ctx.meta
         B, S, F = qkv.shape
         d = F // (3 * h)
-        qkv5 = qkv.view(B, S, h, 3, d)
-        q = qkv5[:, :, :, 0].permute(0, 2, 1, 3)
-        k = qkv5[:, :, :, 1].permute(0, 2, 1, 3)
-        v = qkv5[:, :, :, 2].permute(0, 2, 1, 3)
+        q, k, v = _qkv_views(qkv, h)
         do4 = do.view(B, S, h, d).permute(0, 2, 1, 3)
         o4 = o_buf.view(B, S, h, d).permute(0, 2, 1, 3)
         dqkv = torch.empty_like(qkv)
-        dqkv5 = dqkv.view(B, S, h, 3, d)
+        dq_v, dk_v, dv_v = _qkv_views(dqkv, h)
         if use_hip(qkv):
             # fused MFMA bwd writes straight into the packed dqkv views
-            hip_ops().attn_bwd_out(
-                do4, q, k, v, o4, lse,
-                dqkv5[:, :, :, 0].permute(0, 2, 1, 3),
-                dqkv5[:, :, :, 1].permute(0, 2, 1, 3),
-                dqkv5[:, :, :, 2].permute(0, 2, 1, 3), causal, scale)
+            hip_ops().attn_bwd_out(do4, q, k, v, o4, lse, dq_v, dk_v, dv_v,
+                                   causal, scale)
         else:
             dq, dk, dv = ref.attention_bwd(
                 do4.contiguous(), q.contiguous(), k.contiguous(),
                 v.contiguous(), o4.contiguous(), lse, causal, scale)
-            dqkv5[:, :, :, 0].copy_(dq.permute(0, 2, 1, 3))
-            dqkv5[:, :, :, 1].copy_(dk.permute(0, 2, 1, 3))
-            dqkv5[:, :, :, 2].copy_(dv.permute(0, 2, 1, 3))
+            dq_v.copy_(dq)
+            dk_v.copy_(dk)
+            dv_v.copy_(dv)
         return dqkv, None, None, None
 
 

@@ -7,6 +7,7 @@
 // the same division into its apply_grad jaxpr,
 // shard_parallel/compile_executable.py:272).
 #include "common.h"
+#include "launchers.h"
 
 #define ADAM_CHUNK 16384
 #define ADAM_BLOCK 256

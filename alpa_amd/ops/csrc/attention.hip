@@ -4,21 +4,25 @@
 // Covers the reference's fused-attention slot (SURVEY.md §2.3 kernel table:
 // "batched GEMM + softmax ... fused attention kernel (QK^T->softmax->V)").
 //
-// Structure: 256 threads = 4 waves per block; block owns 64 q rows of one
+// Structure: 512 threads = 8 waves per block; block owns 128 q rows of one
 // (batch, head); wave owns 16 rows.  K tile [64][Dp] and transposed V tile
-// [Dp][64] staged in LDS, shared by all waves; per-wave P tile round-trips
-// through LDS to re-fragment S (C-layout) into the PV A-operand.
+// [Dp][64] staged in LDS, shared by all waves — double-buffered for
+// Dp <= 128, single-buffered for Dp = 256; per-wave P tile round-trips
+// through LDS to re-fragment S (C-layout) into the PV operand.
 //
-// MFMA fragment layouts (verified on hardware by the mfma_probe test):
+// The backward pass (second half of this file) is a deterministic
+// preprocess + dq + dk/dv split with the same block shape.
+//
+// MFMA fragment layouts (verified on hardware by the mfma_probe test,
+// kernels in mfma_probe.hip):
 //   A (16x32): m = lane&15, k = (lane>>4)*8 + j   (j = 0..7)
 //   B (32x16): n = lane&15, k = (lane>>4)*8 + j
 //   C/D      : n = lane&15, m = (lane>>4)*4 + reg (f32x4)
 #include "common.h"
-#include <cstdlib>
+#include "launchers.h"
 
-#define ATTN_BLOCK_Q 64
 #define ATTN_BLOCK_K 64
-#define ATTN_THREADS 1024
+#define ATTN_FWD_THREADS 512
 #define ATTN_BWD_THREADS 512
 
 // Strides are in elements; the innermost (D) dim must be contiguous.
@@ -31,6 +35,12 @@ struct AttnStrides {
   int64_t ob, oh, os;
 };
 
+// s: the launcher's 12-entry array, q(3) k(3) v(3) o(3)
+static AttnStrides attn_strides(const int64_t* s) {
+  return {s[0], s[1], s[2], s[3], s[4], s[5],
+          s[6], s[7], s[8], s[9], s[10], s[11]};
+}
+
 // XCD-aware workgroup swizzle (gfx950: 8 XCDs, hardware assigns
 // workgroup i to XCD i%8, each XCD has its own L2): remap so each XCD
 // gets a CONTIGUOUS run of logical blocks — all blocks of one
@@ -42,21 +52,23 @@ __device__ inline int xcd_swizzle(int flat, int total) {
   return (flat % NXCD) * (total / NXCD) + flat / NXCD;
 }
 
-// ABL: ablation level for perf diagnosis (0 = full kernel; higher skips
-// later phases; asm keep-alives prevent dead-code elimination of earlier
-// phases — guide methodology rule 17)
-template <int Dp, int ABL = 0, bool AL = false, bool VL = false,
-          bool DB = true, int NT = ATTN_THREADS>
-__global__ __launch_bounds__(NT) void attn_fwd_kernel(
+// Dp: head dim padded to the instantiated tile (64/96/128/256); AL: ALiBi
+// bias; VL: per-batch kv lengths (varlen decode).
+template <int Dp, bool AL = false, bool VL = false>
+__global__ __launch_bounds__(ATTN_FWD_THREADS) void attn_fwd_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, short* __restrict__ o,
     float* __restrict__ lse_out, int H, int S, int Skv, int D, float scale,
     int causal, const float* __restrict__ alibi,
     const int* __restrict__ kv_lens, AttnStrides st) {
-  // 8 waves x 16 q-rows = 128 q rows per block; K/V tiles of 64 kv are
-  // double-buffered in LDS with register-prefetched staging (loads for
-  // tile t+1 issue before computing tile t and land after it — the HBM
-  // latency hides under the MFMA/softmax work), one barrier per tile.
+  // 8 waves x 16 q-rows = 128 q rows per block.  For Dp <= 128 the K/V
+  // tiles of 64 kv are double-buffered in LDS with register-prefetched
+  // staging (loads for tile t+1 issue before computing tile t and land
+  // after it — the HBM latency hides under the MFMA/softmax work), one
+  // barrier per tile.  Dp = 256 does not fit two buffers in LDS: it stages
+  // one buffer (85504 B) and pays two barriers per tile.
+  constexpr bool DB = Dp <= 128;
+  constexpr int NT = ATTN_FWD_THREADS;
   constexpr int KSTEPS_QK = Dp / 32;
   constexpr int NTILES = ATTN_BLOCK_K / 16;  // 4
   constexpr int DTILES = Dp / 16;
@@ -87,9 +99,6 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   short* op = o + batch * st.ob + head * st.oh;
   const int q_row0 = qb * (16 * NW) + wave * 16;
 
-  // DB=false: single-buffered K/V (64 KB total for Dp=96 instead of
-  // 91 KB) fits TWO blocks per CU — inter-block latency hiding replaces
-  // the intra-block prefetch (experiment; see profiles/ PMC notes)
   __shared__ short k_lds[DB ? 2 : 1][ATTN_BLOCK_K][Dp + LP];
   __shared__ short vt_lds[DB ? 2 : 1][Dp][ATTN_BLOCK_K + LP];
   __shared__ short p_lds[NW][16][ATTN_BLOCK_K + LP];
@@ -206,13 +215,6 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
       continue;
     }
 
-    if (ABL >= 4) {  // staging-only
-      float keep = bf2f(k_lds[cur][lane][0]) + bf2f(vt_lds[cur][lane][0]);
-      asm volatile("" ::"v"(keep));
-      advance(ti, cur);
-      continue;
-    }
-
 __builtin_amdgcn_s_setprio(1);  // T5: favor the MFMA cluster
     // ---- S^T = K Q^T (A = K tile from LDS, B = Q fragments) ----
     f32x4 s_acc[NTILES];
@@ -229,25 +231,6 @@ __builtin_amdgcn_s_setprio(1);  // T5: favor the MFMA cluster
       s_acc[nt] = acc;
     }
     __builtin_amdgcn_s_setprio(0);
-
-    if (ABL >= 3) {  // QK^T only
-#pragma unroll
-      for (int nt = 0; nt < NTILES; ++nt)
-        asm volatile("" ::"v"(s_acc[nt][0]), "v"(s_acc[nt][3]));
-      advance(ti, cur);
-      continue;
-    }
-    if (ABL == 2) {  // no softmax math: raw S write + one read
-#pragma unroll
-      for (int nt = 0; nt < NTILES; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          p_lds[wave][lo][nt * 16 + hi * 4 + r] = f2bf(s_acc[nt][r]);
-      bf16x8 a0 = *reinterpret_cast<const bf16x8*>(&p_lds[wave][lo][hi * 8]);
-      asm volatile("" ::"v"(a0));
-      advance(ti, cur);
-      continue;
-    }
 
     // ---- mask + scale + lane-local max over this lane's 16 kv ----
     float tile_max = -INFINITY;
@@ -307,12 +290,6 @@ __builtin_amdgcn_s_setprio(1);  // T5: favor the MFMA cluster
     part += __shfl_xor(part, 32, 64);
     l_state += part;
 
-    if (ABL >= 1) {
-      asm volatile("" ::"v"(l_state), "v"(m_state));
-      advance(ti, cur);
-      continue;
-    }
-
 __builtin_amdgcn_s_setprio(1);  // T5: favor the MFMA cluster
     // ---- O^T += V^T P^T  (A = V^T from vt_lds, B = P^T from p_lds) ----
 #pragma unroll
@@ -353,295 +330,7 @@ __builtin_amdgcn_s_setprio(1);  // T5: favor the MFMA cluster
   }
 }
 
-// ===========================================================================
-// 32x32x16-MFMA forward variant (EXPERIMENTAL, measured SLOWER: 570us vs
-// 272us at the bench shape).  Wave owns 32 q rows; 16 waves per block.
-// Numerically verified (maxdiff 2e-3 vs v1).  Why it loses: 1024-thread
-// blocks require 4 waves/SIMD residency, capping VGPR at 128, while the
-// f32x16 accumulators want ~150 — the compiler spills 272 B/lane to
-// scratch.  The path forward (round 2) is keeping P in registers via
-// permlane exchanges to shed the accumulator+LDS round-trip pressure.
-// Kept as a measured data point + layout reference (mfma_probe32).
-// ===========================================================================
-#define ATTN32_THREADS 1024
-
-template <int Dp, bool AL = false>
-__global__ __launch_bounds__(ATTN32_THREADS) void attn_fwd_kernel32(
-    const short* __restrict__ q, const short* __restrict__ k,
-    const short* __restrict__ v, short* __restrict__ o,
-    float* __restrict__ lse_out, int H, int S, int Skv, int D, float scale,
-    int causal, const float* __restrict__ alibi, AttnStrides st) {
-  constexpr int KS_QK = Dp / 16;       // k-steps over head dim (K=16)
-  constexpr int MT = 2;                // 2 kv m-tiles of 32 per 64-kv tile
-  constexpr int DT = Dp / 32;          // d tiles of 32 (O^T rows)
-  constexpr int LP = 4;
-  constexpr int NW = ATTN32_THREADS / 64;  // 16 waves
-  constexpr int GPR = Dp / 8;
-  constexpr int TOTAL_G = 64 * GPR;
-
-  const int qb = blockIdx.x;
-  const int bh = blockIdx.y;
-  const int batch = bh / H, head = bh % H;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int lo = lane & 31;            // q column / m row (32-wide)
-  const int hi = lane >> 5;            // 0/1
-
-  const short* qp = q + batch * st.qb + head * st.qh;
-  const short* kp = k + batch * st.kb + head * st.kh;
-  const short* vp = v + batch * st.vb + head * st.vh;
-  short* op = o + batch * st.ob + head * st.oh;
-  const int q_row0 = qb * (32 * NW) + wave * 32;
-  const int my_q = q_row0 + lo;
-  const float al_slope = AL ? alibi[head] : 0.f;
-  const int al_qoff = Skv - S;
-
-  __shared__ short k_lds[2][64][Dp + LP];
-  __shared__ short vt_lds[2][Dp][64 + LP];
-  __shared__ short p_lds[NW][32][64 + LP];
-
-  // Q fragments (B-operand): q_frag[ks][j] = Q[my_q][ks*16 + hi*8 + j]
-  bf16x8 q_frag[KS_QK];
-  {
-    int row = min(my_q, S - 1);
-#pragma unroll
-    for (int ks = 0; ks < KS_QK; ++ks) {
-      int col = ks * 16 + hi * 8;
-      bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-      q_frag[ks] = z;
-      if (col + 8 <= D)
-        q_frag[ks] =
-            *reinterpret_cast<const bf16x8*>(qp + (int64_t)row * st.qs + col);
-    }
-  }
-
-  float m_state = -INFINITY, l_state = 0.f;
-  f32x16 o_acc[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) o_acc[dt] = f32x16{};
-
-  const int kv_limit = causal ? min(Skv, qb * (32 * NW) + 32 * NW) : Skv;
-  const int n_tiles = (kv_limit + 63) / 64;
-
-  bf16x8 kreg[2], vreg[2];
-  auto issue_loads = [&](int tile) {
-    int t = threadIdx.x;
-    bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-    kreg[0] = kreg[1] = vreg[0] = vreg[1] = z;
-    if (t < TOTAL_G / 2) {
-      int kvr = (t / GPR) * 2, dg = (t % GPR) * 8;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        int src = tile * 64 + kvr + u;
-        if (src < Skv && dg + 8 <= D) {
-          kreg[u] = *reinterpret_cast<const bf16x8*>(
-              kp + (int64_t)src * st.ks + dg);
-          vreg[u] = *reinterpret_cast<const bf16x8*>(
-              vp + (int64_t)src * st.vs + dg);
-        }
-      }
-    }
-  };
-  auto write_tile = [&](int buf) {
-    int t = threadIdx.x;
-    if (t < TOTAL_G / 2) {
-      int kvr = (t / GPR) * 2, dg = (t % GPR) * 8;
-      *reinterpret_cast<bf16x8*>(&k_lds[buf][kvr][dg]) = kreg[0];
-      *reinterpret_cast<bf16x8*>(&k_lds[buf][kvr + 1][dg]) = kreg[1];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        short2 pr;
-        pr.x = vreg[0][j];
-        pr.y = vreg[1][j];
-        *reinterpret_cast<short2*>(&vt_lds[buf][dg + j][kvr]) = pr;
-      }
-    }
-  };
-
-  if (n_tiles > 0) {
-    issue_loads(0);
-    write_tile(0);
-    __syncthreads();
-  }
-
-  for (int ti = 0; ti < n_tiles; ++ti) {
-    const int kvb = ti * 64;
-    const int cur = ti & 1;
-    if (ti + 1 < n_tiles) issue_loads(ti + 1);
-
-    if (causal && kvb > q_row0 + 31) {
-      if (ti + 1 < n_tiles) { write_tile(1 - cur); __syncthreads(); }
-      continue;
-    }
-
-    // ---- S^T = K Q^T: A = K (m=kv), B = q_frag ----
-    f32x16 s_acc[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      f32x16 acc = {};
-#pragma unroll
-      for (int ks = 0; ks < KS_QK; ++ks) {
-        bf16x8 a = *reinterpret_cast<const bf16x8*>(
-            &k_lds[cur][mt * 32 + lo][ks * 16 + hi * 8]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, q_frag[ks], acc, 0,
-                                                      0, 0);
-      }
-      s_acc[mt] = acc;
-    }
-
-    // ---- mask + scale + lane-local max (32 values for q = my_q) ----
-    float tile_max = -INFINITY;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int kv_idx = kvb + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        float sv = s_acc[mt][r] * scale;
-        if (AL) sv = fmaf(al_slope, (float)(kv_idx - my_q - al_qoff), sv);
-        bool masked = (kv_idx >= Skv) || (causal && kv_idx > my_q) ||
-                      (my_q >= S);
-        sv = masked ? -INFINITY : sv;
-        s_acc[mt][r] = sv;
-        tile_max = fmaxf(tile_max, sv);
-      }
-    }
-    tile_max = fmaxf(tile_max, __shfl_xor(tile_max, 32, 64));
-
-    float m_new = fmaxf(m_state, tile_max);
-    float alpha = (m_state == -INFINITY) ? 0.f : __expf(m_state - m_new);
-    m_state = m_new;
-    l_state *= alpha;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o_acc[dt][r] *= alpha;
-
-    float part = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float pval = (s_acc[mt][r] == -INFINITY)
-                         ? 0.f
-                         : __expf(s_acc[mt][r] - m_state);
-        part += pval;
-        p_lds[wave][lo][mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi] =
-            f2bf(pval);
-      }
-    }
-    part += __shfl_xor(part, 32, 64);
-    l_state += part;
-
-    // ---- O^T += V^T P^T: A = V^T (m=d), B = P^T (n=q) ----
-#pragma unroll
-    for (int ks = 0; ks < 64 / 16; ++ks) {
-      bf16x8 b = *reinterpret_cast<const bf16x8*>(
-          &p_lds[wave][lo][ks * 16 + hi * 8]);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        bf16x8 a = *reinterpret_cast<const bf16x8*>(
-            &vt_lds[cur][dt * 32 + lo][ks * 16 + hi * 8]);
-        o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, o_acc[dt],
-                                                            0, 0, 0);
-      }
-    }
-
-    if (ti + 1 < n_tiles) {
-      write_tile(1 - cur);
-      __syncthreads();
-    }
-  }
-
-  // ---- epilogue: lane holds O^T[d = dt*32 + (r&3)+8*(r>>2)+4*hi][my_q] --
-  if (my_q < S) {
-    float inv_l = (l_state > 0.f) ? 1.0f / l_state : 0.f;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int col = dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        if (col < D)
-          op[(int64_t)my_q * st.os + col] = f2bf(o_acc[dt][r] * inv_l);
-      }
-    }
-    if (hi == 0 && lse_out != nullptr)
-      lse_out[(int64_t)bh * S + my_q] =
-          (l_state > 0.f) ? m_state + __logf(l_state) : -INFINITY;
-  }
-}
-
 extern "C" {
-
-hipError_t launch_attn_fwd_ablate(const void* q, const void* k,
-                                  const void* v, void* o, float* lse,
-                                  int64_t B, int64_t H, int64_t S,
-                                  int64_t Skv, int64_t D, float scale,
-                                  int causal, const int64_t* strides,
-                                  int abl, hipStream_t stream) {
-  dim3 grid((uint32_t)ceil_div(S, 16 * (ATTN_THREADS / 64)), (uint32_t)(B * H));
-  dim3 block(ATTN_THREADS);
-  AttnStrides st;
-  st.qb = strides[0]; st.qh = strides[1]; st.qs = strides[2];
-  st.kb = strides[3]; st.kh = strides[4]; st.ks = strides[5];
-  st.vb = strides[6]; st.vh = strides[7]; st.vs = strides[8];
-  st.ob = strides[9]; st.oh = strides[10]; st.os = strides[11];
-  if (D > 96) return hipErrorInvalidValue;
-#define ABL_CASE(A)                                                         \
-  if (abl == A) {                                                           \
-    attn_fwd_kernel<96, A><<<grid, block, 0, stream>>>(                     \
-        (const short*)q, (const short*)k, (const short*)v, (short*)o, lse,  \
-        (int)H, (int)S, (int)Skv, (int)D, scale, causal, nullptr, nullptr, \
-        st);                                                                \
-  }
-  ABL_CASE(0) ABL_CASE(1) ABL_CASE(2) ABL_CASE(3) ABL_CASE(4)
-#undef ABL_CASE
-  return hipGetLastError();
-}
-
-hipError_t launch_attn_fwd_v2(const void* q, const void* k, const void* v,
-                              void* o, float* lse, int64_t B, int64_t H,
-                              int64_t S, int64_t Skv, int64_t D, float scale,
-                              int causal, const int64_t* strides,
-                              hipStream_t stream) {
-  dim3 grid((uint32_t)ceil_div(S, 32 * (ATTN32_THREADS / 64)),
-            (uint32_t)(B * H));
-  dim3 block(ATTN32_THREADS);
-  AttnStrides st;
-  st.qb = strides[0]; st.qh = strides[1]; st.qs = strides[2];
-  st.kb = strides[3]; st.kh = strides[4]; st.ks = strides[5];
-  st.vb = strides[6]; st.vh = strides[7]; st.vs = strides[8];
-  st.ob = strides[9]; st.oh = strides[10]; st.os = strides[11];
-  if (D <= 64) {
-    attn_fwd_kernel32<64><<<grid, block, 0, stream>>>(
-        (const short*)q, (const short*)k, (const short*)v, (short*)o, lse,
-        (int)H, (int)S, (int)Skv, (int)D, scale, causal, nullptr, st);
-  } else if (D <= 96) {
-    attn_fwd_kernel32<96><<<grid, block, 0, stream>>>(
-        (const short*)q, (const short*)k, (const short*)v, (short*)o, lse,
-        (int)H, (int)S, (int)Skv, (int)D, scale, causal, nullptr, st);
-  } else if (D <= 128) {
-    attn_fwd_kernel32<128><<<grid, block, 0, stream>>>(
-        (const short*)q, (const short*)k, (const short*)v, (short*)o, lse,
-        (int)H, (int)S, (int)Skv, (int)D, scale, causal, nullptr, st);
-  } else {
-    return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-static int attn_fwd_nt() {
-  // block size selection: 512 threads (8 waves) fits TWO blocks per CU
-  // at Dp=96 double-buffered (72.6 KB LDS each) — cross-block overlap
-  // hides the per-tile barriers that a single 16-wave block serializes.
-  // Override with ALPA_ATTN_FWD_NT=1024 for the round-1 shape.
-  static int nt = -1;
-  if (nt < 0) {
-    const char* e = getenv("ALPA_ATTN_FWD_NT");
-    nt = e ? atoi(e) : 512;
-    if (nt != 512 && nt != 1024) nt = 512;
-  }
-  return nt;
-}
 
 hipError_t launch_attn_fwd(const void* q, const void* k, const void* v,
                            void* o, float* lse, int64_t B, int64_t H,
@@ -649,44 +338,21 @@ hipError_t launch_attn_fwd(const void* q, const void* k, const void* v,
                            int causal, const float* alibi,
                            const int* kv_lens, const int64_t* strides,
                            hipStream_t stream) {
-  const int NTsel = attn_fwd_nt();
-  dim3 grid((uint32_t)ceil_div(S, 16 * (NTsel / 64)), (uint32_t)(B * H));
-  dim3 block(NTsel);
-#define FWD_VARIANT(DP, ALB, VLB, ALP, VLP)                                \
-  do {                                                                     \
-    if (NTsel == 512)                                                      \
-      attn_fwd_kernel<DP, 0, ALB, VLB, true, 512>                          \
-          <<<grid, block, 0, stream>>>(                                    \
-              (const short*)q, (const short*)k, (const short*)v,           \
-              (short*)o, lse, (int)H, (int)S, (int)Skv, (int)D, scale,     \
-              causal, ALP, VLP, st);                                       \
-    else                                                                   \
-      attn_fwd_kernel<DP, 0, ALB, VLB, true, 1024>                         \
-          <<<grid, block, 0, stream>>>(                                    \
-              (const short*)q, (const short*)k, (const short*)v,           \
-              (short*)o, lse, (int)H, (int)S, (int)Skv, (int)D, scale,     \
-              causal, ALP, VLP, st);                                       \
-  } while (0)
+  const AttnStrides st = attn_strides(strides);
+  dim3 grid((uint32_t)ceil_div(S, 16 * (ATTN_FWD_THREADS / 64)),
+            (uint32_t)(B * H));
+  dim3 block(ATTN_FWD_THREADS);
+#define FWD_LAUNCH(DP, ALB, VLB)                                           \
+  attn_fwd_kernel<DP, ALB, VLB><<<grid, block, 0, stream>>>(               \
+      (const short*)q, (const short*)k, (const short*)v, (short*)o, lse,   \
+      (int)H, (int)S, (int)Skv, (int)D, scale, causal, alibi, kv_lens, st)
 #define FWD_DISPATCH(DP)                                                   \
   do {                                                                     \
-    if (alibi && kv_lens) FWD_VARIANT(DP, true, true, alibi, kv_lens);     \
-    else if (alibi) FWD_VARIANT(DP, true, false, alibi, nullptr);          \
-    else if (kv_lens) FWD_VARIANT(DP, false, true, nullptr, kv_lens);      \
-    else FWD_VARIANT(DP, false, false, nullptr, nullptr);                  \
+    if (alibi && kv_lens) FWD_LAUNCH(DP, true, true);                      \
+    else if (alibi) FWD_LAUNCH(DP, true, false);                           \
+    else if (kv_lens) FWD_LAUNCH(DP, false, true);                         \
+    else FWD_LAUNCH(DP, false, false);                                     \
   } while (0)
-  AttnStrides st;
-  st.qb = strides[0];
-  st.qh = strides[1];
-  st.qs = strides[2];
-  st.kb = strides[3];
-  st.kh = strides[4];
-  st.ks = strides[5];
-  st.vb = strides[6];
-  st.vh = strides[7];
-  st.vs = strides[8];
-  st.ob = strides[9];
-  st.oh = strides[10];
-  st.os = strides[11];
   if (D <= 64) {
     FWD_DISPATCH(64);
   } else if (D <= 96) {
@@ -694,113 +360,18 @@ hipError_t launch_attn_fwd(const void* q, const void* k, const void* v,
   } else if (D <= 128) {
     FWD_DISPATCH(128);
   } else if (D <= 256 && !alibi && !kv_lens) {
-    // split-D experiment for CodeGen-class heads: single-buffered K/V
-    // (85.5 KB LDS at Dp=256), 512 threads; register tiling carries 16
-    // o_acc f32x4 — expect low occupancy, measured against the blocked
-    // hipBLASLt path before becoming the default (ROUND2 item 4)
-    dim3 grid2((uint32_t)ceil_div(S, 16 * 8), (uint32_t)(B * H));
-    attn_fwd_kernel<256, 0, false, false, false, 512>
-        <<<grid2, dim3(512), 0, stream>>>(
-            (const short*)q, (const short*)k, (const short*)v, (short*)o,
-            lse, (int)H, (int)S, (int)Skv, (int)D, scale, causal,
-            nullptr, nullptr, st);
+    // CodeGen-class heads: the plain variant only, single-buffered K/V;
+    // the 16 o_acc f32x4 per lane keep occupancy low
+    FWD_LAUNCH(256, false, false);
   } else {
     return hipErrorInvalidValue;
   }
 #undef FWD_DISPATCH
-#undef FWD_VARIANT
-  return hipGetLastError();
-}
-
-// Single-buffer experiment entry (plain path only: no alibi/varlen)
-hipError_t launch_attn_fwd_sbuf(const void* q, const void* k, const void* v,
-                                void* o, float* lse, int64_t B, int64_t H,
-                                int64_t S, int64_t Skv, int64_t D,
-                                float scale, int causal,
-                                const int64_t* strides,
-                                hipStream_t stream) {
-  // 512 threads + single-buffered K/V = 43.25 KB LDS at Dp=96 ->
-  // THREE blocks per CU (24 waves); cross-block overlap replaces the
-  // intra-block prefetch
-  dim3 grid((uint32_t)ceil_div(S, 16 * (512 / 64)), (uint32_t)(B * H));
-  dim3 block(512);
-  AttnStrides st;
-  st.qb = strides[0]; st.qh = strides[1]; st.qs = strides[2];
-  st.kb = strides[3]; st.kh = strides[4]; st.ks = strides[5];
-  st.vb = strides[6]; st.vh = strides[7]; st.vs = strides[8];
-  st.ob = strides[9]; st.oh = strides[10]; st.os = strides[11];
-#define SBUF_CASE(DP)                                                      \
-  attn_fwd_kernel<DP, 0, false, false, false, 512>                         \
-      <<<grid, block, 0, stream>>>(                                        \
-      (const short*)q, (const short*)k, (const short*)v, (short*)o, lse,   \
-      (int)H, (int)S, (int)Skv, (int)D, scale, causal, nullptr, nullptr,   \
-      st)
-  if (D <= 64) SBUF_CASE(64);
-  else if (D <= 96) SBUF_CASE(96);
-  else if (D <= 128) SBUF_CASE(128);
-  else return hipErrorInvalidValue;
-#undef SBUF_CASE
+#undef FWD_LAUNCH
   return hipGetLastError();
 }
 
 }  // extern "C"
-
-// ---------------------------------------------------------------------------
-// MFMA layout probe: D = A @ B for a single 16x32 x 32x16 tile, to verify
-// the fragment layouts above against a CPU reference on real hardware.
-__global__ void mfma_probe_kernel(const short* __restrict__ a,
-                                  const short* __restrict__ b,
-                                  float* __restrict__ d) {
-  int lane = threadIdx.x & 63;
-  int lo = lane & 15, hi = lane >> 4;
-  bf16x8 af, bf;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    af[j] = a[lo * 32 + hi * 8 + j];       // A[m][k] row-major 16x32
-    bf[j] = b[(hi * 8 + j) * 16 + lo];     // B[k][n] row-major 32x16
-  }
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc, 0, 0, 0);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) d[(hi * 4 + r) * 16 + lo] = acc[r];
-}
-
-extern "C" hipError_t launch_mfma_probe(const void* a, const void* b,
-                                        float* d, hipStream_t stream) {
-  mfma_probe_kernel<<<dim3(1), dim3(64), 0, stream>>>((const short*)a,
-                                                      (const short*)b, d);
-  return hipGetLastError();
-}
-
-// 32x32x16 layout probe: D(32x32) = A(32x16) @ B(16x32).
-// Assumed layouts: A: m=lane&31, k=(lane>>5)*8+j; B: n=lane&31, same k;
-// C/D (documented, guide §3): col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5)
-__global__ void mfma_probe32_kernel(const short* __restrict__ a,
-                                    const short* __restrict__ b,
-                                    float* __restrict__ d) {
-  int lane = threadIdx.x & 63;
-  int lo = lane & 31, hi = lane >> 5;
-  bf16x8 af, bf;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    af[j] = a[lo * 16 + hi * 8 + j];
-    bf[j] = b[(hi * 8 + j) * 32 + lo];
-  }
-  f32x16 acc = {};
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, acc, 0, 0, 0);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
-    d[row * 32 + lo] = acc[r];
-  }
-}
-
-extern "C" hipError_t launch_mfma_probe32(const void* a, const void* b,
-                                          float* d, hipStream_t stream) {
-  mfma_probe32_kernel<<<dim3(1), dim3(64), 0, stream>>>((const short*)a,
-                                                        (const short*)b, d);
-  return hipGetLastError();
-}
 
 // ===========================================================================
 // Flash attention BACKWARD (bf16, causal/full), deterministic two-kernel
@@ -821,6 +392,14 @@ struct AttnBwdStrides {
   int64_t dkb, dkh, dks;
   int64_t dvb, dvh, dvs;
 };
+
+// s: the launcher's 24-entry array, q(3) k(3) v(3) do(3) dq(3) dk(3) dv(3)
+// o(3); the o strides s[21..23] go to the preprocess kernel only
+static AttnBwdStrides attn_bwd_strides(const int64_t* s) {
+  return {s[0],  s[1],  s[2],  s[3],  s[4],  s[5],  s[6],
+          s[7],  s[8],  s[9],  s[10], s[11], s[12], s[13],
+          s[14], s[15], s[16], s[17], s[18], s[19], s[20]};
+}
 
 __global__ void attn_bwd_preprocess_kernel(const short* __restrict__ dout,
                                            const short* __restrict__ o,
@@ -854,9 +433,9 @@ __global__ void attn_bwd_preprocess_kernel(const short* __restrict__ dout,
 }
 
 // ---------------------------------------------------------------- dq kernel
-// Block: 4 waves, 64 q rows; loops kv blocks of 64.
+// Block: 8 waves, 128 q rows; loops kv tiles of 64.
 //   S = Q K^T          (A=Q regs, B=K_lds row-major)
-//   P = exp(S*? - lse) (lse already includes the scale from fwd)
+//   P = exp(S*scale - lse)
 //   dP = dO V^T        (A=dO regs, B=V_lds row-major)
 //   dS = P*(dP-delta)*scale
 //   dQ += dS K         (A=dS via p_lds, B=Kt_lds transposed)
@@ -1064,7 +643,7 @@ __builtin_amdgcn_s_setprio(1);  // T5: favor the MFMA cluster
 }
 
 // ------------------------------------------------------------- dk/dv kernel
-// Block: 4 waves, 64 kv rows; loops q blocks of 64 (from the diagonal for
+// Block: 8 waves, 128 kv rows; loops q tiles of 64 (from the diagonal for
 // causal).
 //   S^T = K Q^T        (A=K regs, B=Q_lds row-major)
 //   P^T = exp(S^T*scale - lse[q])
@@ -1072,7 +651,7 @@ __builtin_amdgcn_s_setprio(1);  // T5: favor the MFMA cluster
 //   dP^T = V dO^T      (A=V regs, B=dO_lds row-major)
 //   dS^T = P^T*(dP^T - delta[q])*scale
 //   dK += dS^T Q       (A=dS^T via p_lds, B=Qt_lds)
-template <int Dp, int ABL = 0, bool AL = false, bool LEAN = false>
+template <int Dp, bool AL = false>
 __global__ __launch_bounds__(ATTN_BWD_THREADS) void attn_bwd_dkv_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, const short* __restrict__ dout,
@@ -1113,11 +692,8 @@ __global__ __launch_bounds__(ATTN_BWD_THREADS) void attn_bwd_dkv_kernel(
 
   __shared__ short q_lds[64][Dp + LP];
   __shared__ short do_lds[64][Dp + LP];
-  // LEAN: drop the transposed Q/dO tiles (-27.6 KB LDS => 3 blocks/CU)
-  // and gather the dV/dK B-fragments from the row-major tiles with
-  // strided b16 reads instead (occupancy-vs-LDS-op-count experiment)
-  __shared__ short qt_lds[LEAN ? 1 : Dp][64 + LP];
-  __shared__ short dot_lds[LEAN ? 1 : Dp][64 + LP];
+  __shared__ short qt_lds[Dp][64 + LP];
+  __shared__ short dot_lds[Dp][64 + LP];
   __shared__ short p_lds[NW][16][64 + LP];
   __shared__ float lse_lds[64];
   __shared__ float delta_lds[64];
@@ -1187,17 +763,15 @@ __global__ __launch_bounds__(ATTN_BWD_THREADS) void attn_bwd_dkv_kernel(
       *reinterpret_cast<bf16x8*>(&q_lds[qr + 1][dg]) = qreg[1];
       *reinterpret_cast<bf16x8*>(&do_lds[qr][dg]) = doreg[0];
       *reinterpret_cast<bf16x8*>(&do_lds[qr + 1][dg]) = doreg[1];
-      if (!LEAN) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          short2 pq, pd;
-          pq.x = qreg[0][j];
-          pq.y = qreg[1][j];
-          pd.x = doreg[0][j];
-          pd.y = doreg[1][j];
-          *reinterpret_cast<short2*>(&qt_lds[dg + j][qr]) = pq;
-          *reinterpret_cast<short2*>(&dot_lds[dg + j][qr]) = pd;
-        }
+      for (int j = 0; j < 8; ++j) {
+        short2 pq, pd;
+        pq.x = qreg[0][j];
+        pq.y = qreg[1][j];
+        pd.x = doreg[0][j];
+        pd.y = doreg[1][j];
+        *reinterpret_cast<short2*>(&qt_lds[dg + j][qr]) = pq;
+        *reinterpret_cast<short2*>(&dot_lds[dg + j][qr]) = pd;
       }
     }
     if (t < 64) {
@@ -1223,14 +797,6 @@ __global__ __launch_bounds__(ATTN_BWD_THREADS) void attn_bwd_dkv_kernel(
       continue;
     }
 
-    if (ABL >= 3) {  // staging only
-      float keep = bf2f(q_lds[lane & 63][0]) + bf2f(do_lds[0][lane & 63]) +
-                   bf2f(q_lds[0][lane & 63]) + bf2f(do_lds[lane & 63][0]);
-      asm volatile("" ::"v"(keep));
-      __syncthreads();
-      if (ti + 1 < n_tiles) { write_tile(); __syncthreads(); }
-      continue;
-    }
 __builtin_amdgcn_s_setprio(1);  // T5
     // S^T and dP^T tiles (C: row = kv (hi*4+r), col = q (nt*16+lo))
     f32x4 st_acc[NT], dpt_acc[NT];
@@ -1274,61 +840,34 @@ __builtin_amdgcn_s_setprio(1);  // T5
       }
     }
 
-    if (ABL >= 2) {  // S^T/dP^T + softmax math only
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-        asm volatile("" ::"v"((int)dst_pk[nt][0]), "v"((int)dst_pk[nt][3]));
-      __syncthreads();
-      if (ti + 1 < n_tiles) { write_tile(); __syncthreads(); }
-      continue;
-    }
 __builtin_amdgcn_s_setprio(1);  // T5
     // dV += P^T @ dO (A = P^T via p_lds, B = dOt).  The dS^T spill for
     // the dK group is INTERLEAVED into this loop: after dV's ks-th read
     // drains q-columns [32ks, 32ks+32), those p_lds columns are dead and
     // dS^T for tiles nt = 2ks, 2ks+1 overwrites them (same-wave LDS ops
     // complete in issue order, so no barrier is needed).  Measured
-    // NEUTRAL on the bench shape — the ablation's "+206 us dK phase" is
-    // tail LATENCY (any last MFMA group absorbs the drain into the
-    // barrier), not a write->read stall — kept because it frees the
-    // dst_pk registers before the dK group.  The remaining bwd levers
-    // are structural: 3 blocks/CU via T10 hardware-transpose reads of
-    // q/do (dropping qt/dot tiles, -27.6 KB LDS), or FA2-style dq
-    // accumulation by atomics inside this kernel (kills the separate dq
-    // kernel's S/dP recompute at the cost of fp32 atomics).
+    // neutral on the bench shape (the dK phase's cost is tail latency
+    // absorbed into the barrier, not a write->read stall); kept because
+    // it frees the dst_pk registers before the dK group.
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 a = *reinterpret_cast<const bf16x8*>(
           &p_lds[wave][lo][ks * 32 + hi * 8]);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        bf16x8 b;
-        if (LEAN) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            b[j] = do_lds[ks * 32 + hi * 8 + j][dt * 16 + lo];
-        } else {
-          b = *reinterpret_cast<const bf16x8*>(
-              &dot_lds[dt * 16 + lo][ks * 32 + hi * 8]);
-        }
+        bf16x8 b = *reinterpret_cast<const bf16x8*>(
+            &dot_lds[dt * 16 + lo][ks * 32 + hi * 8]);
         dv_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             a, b, dv_acc[dt], 0, 0, 0);
       }
-      if (ABL == 0) {
 #pragma unroll
-        for (int nt = 2 * ks; nt < 2 * ks + 2; ++nt)
+      for (int nt = 2 * ks; nt < 2 * ks + 2; ++nt)
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            p_lds[wave][hi * 4 + r][nt * 16 + lo] = dst_pk[nt][r];
-      }
+        for (int r = 0; r < 4; ++r)
+          p_lds[wave][hi * 4 + r][nt * 16 + lo] = dst_pk[nt][r];
     }
     __builtin_amdgcn_s_setprio(0);
 
-    if (ABL >= 1) {  // skip the dK group
-      __syncthreads();
-      if (ti + 1 < n_tiles) { write_tile(); __syncthreads(); }
-      continue;
-    }
     // dK += dS^T @ Q (A = dS^T via p_lds, B = Qt)
 __builtin_amdgcn_s_setprio(1);  // T5
 #pragma unroll
@@ -1337,15 +876,8 @@ __builtin_amdgcn_s_setprio(1);  // T5
           &p_lds[wave][lo][ks * 32 + hi * 8]);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        bf16x8 b;
-        if (LEAN) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            b[j] = q_lds[ks * 32 + hi * 8 + j][dt * 16 + lo];
-        } else {
-          b = *reinterpret_cast<const bf16x8*>(
-              &qt_lds[dt * 16 + lo][ks * 32 + hi * 8]);
-        }
+        bf16x8 b = *reinterpret_cast<const bf16x8*>(
+            &qt_lds[dt * 16 + lo][ks * 32 + hi * 8]);
         dk_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             a, b, dk_acc[dt], 0, 0, 0);
       }
@@ -1376,38 +908,6 @@ __builtin_amdgcn_s_setprio(1);  // T5
 
 extern "C" {
 
-hipError_t launch_attn_bwd_dkv_ablate(const void* q, const void* k,
-                                      const void* v, const void* dout,
-                                      const float* lse, const float* delta,
-                                      void* dk, void* dv, int64_t B,
-                                      int64_t H, int64_t S, int64_t Skv,
-                                      int64_t D, float scale, int causal,
-                                      const int64_t* strides, int abl,
-                                      hipStream_t stream) {
-  AttnBwdStrides st;
-  const int64_t* pp = strides;
-  st.qb = pp[0]; st.qh = pp[1]; st.qs = pp[2];
-  st.kb = pp[3]; st.kh = pp[4]; st.ks = pp[5];
-  st.vb = pp[6]; st.vh = pp[7]; st.vs = pp[8];
-  st.dob = pp[9]; st.doh = pp[10]; st.dos = pp[11];
-  st.dqb = pp[12]; st.dqh = pp[13]; st.dqs = pp[14];
-  st.dkb = pp[15]; st.dkh = pp[16]; st.dks = pp[17];
-  st.dvb = pp[18]; st.dvh = pp[19]; st.dvs = pp[20];
-  dim3 block(ATTN_BWD_THREADS);
-  dim3 grid_kv((uint32_t)ceil_div(Skv, 16 * (ATTN_BWD_THREADS / 64)),
-               (uint32_t)(B * H));
-  if (D > 96) return hipErrorInvalidValue;
-#define DKV_CASE(A)                                                        \
-  if (abl == A)                                                            \
-    attn_bwd_dkv_kernel<96, A><<<grid_kv, block, 0, stream>>>(             \
-        (const short*)q, (const short*)k, (const short*)v,                 \
-        (const short*)dout, lse, delta, (short*)dk, (short*)dv, (int)H,    \
-        (int)S, (int)Skv, (int)D, scale, causal, nullptr, st);
-  DKV_CASE(0) DKV_CASE(1) DKV_CASE(2) DKV_CASE(3)
-#undef DKV_CASE
-  return hipGetLastError();
-}
-
 hipError_t launch_attn_bwd(const void* q, const void* k, const void* v,
                            const void* o, const void* dout,
                            const float* lse, float* delta_ws, void* dq,
@@ -1415,23 +915,17 @@ hipError_t launch_attn_bwd(const void* q, const void* k, const void* v,
                            int64_t S, int64_t Skv, int64_t D, float scale,
                            int causal, const float* alibi,
                            const int64_t* strides, hipStream_t stream) {
-  // strides layout: q(3) k(3) v(3) do(3) dq(3) dk(3) dv(3) o(3)
-  AttnBwdStrides st;
-  const int64_t* p = strides;
-  st.qb = p[0]; st.qh = p[1]; st.qs = p[2];
-  st.kb = p[3]; st.kh = p[4]; st.ks = p[5];
-  st.vb = p[6]; st.vh = p[7]; st.vs = p[8];
-  st.dob = p[9]; st.doh = p[10]; st.dos = p[11];
-  st.dqb = p[12]; st.dqh = p[13]; st.dqs = p[14];
-  st.dkb = p[15]; st.dkh = p[16]; st.dks = p[17];
-  st.dvb = p[18]; st.dvh = p[19]; st.dvs = p[20];
+  // reject before anything is enqueued
+  if (D > 128) return hipErrorInvalidValue;
+  const AttnBwdStrides st = attn_bwd_strides(strides);
   int64_t rows = B * H * S;
   {
     dim3 block(256);
     dim3 grid((uint32_t)ceil_div(rows, 16));  // 16 rows per 256-thr block
     attn_bwd_preprocess_kernel<<<grid, block, 0, stream>>>(
         (const short*)dout, (const short*)o, delta_ws, rows, (int)H, (int)S,
-        (int)D, st.dob, st.doh, st.dos, p[21], p[22], p[23]);
+        (int)D, st.dob, st.doh, st.dos, strides[21], strides[22],
+        strides[23]);
   }
   // dq and dkv are independent (disjoint outputs, shared read-only
   // inputs) and each runs at ~3 waves/SIMD — launching them on two
@@ -1450,40 +944,31 @@ hipError_t launch_attn_bwd(const void* q, const void* k, const void* v,
               (uint32_t)(B * H));
   dim3 grid_kv((uint32_t)ceil_div(Skv, 16 * (ATTN_BWD_THREADS / 64)),
                (uint32_t)(B * H));
-#define LAUNCH_BWD_T(DP, ALB, ALP)                                         \
-  do {                                                                       \
-    attn_bwd_dq_kernel<DP, ALB><<<grid_q, block, 0, side_stream>>>(          \
-        (const short*)q, (const short*)k, (const short*)v,                   \
-        (const short*)dout, lse, delta_ws, (short*)dq, (int)H, (int)S,       \
-        (int)Skv, (int)D, scale, causal, ALP, st);                           \
-    if (getenv("ALPA_ATTN_DKV_LEAN") &&                                      \
-        getenv("ALPA_ATTN_DKV_LEAN")[0] == '1')                              \
-      attn_bwd_dkv_kernel<DP, 0, ALB, true>                                  \
-          <<<grid_kv, block, 0, stream>>>(                                   \
-              (const short*)q, (const short*)k, (const short*)v,             \
-              (const short*)dout, lse, delta_ws, (short*)dk, (short*)dv,     \
-              (int)H, (int)S, (int)Skv, (int)D, scale, causal, ALP, st);     \
-    else                                                                     \
-      attn_bwd_dkv_kernel<DP, 0, ALB><<<grid_kv, block, 0, stream>>>(        \
-        (const short*)q, (const short*)k, (const short*)v,                   \
-        (const short*)dout, lse, delta_ws, (short*)dk, (short*)dv, (int)H,   \
-        (int)S, (int)Skv, (int)D, scale, causal, ALP, st);                   \
+#define LAUNCH_BWD_T(DP, ALB)                                              \
+  do {                                                                     \
+    attn_bwd_dq_kernel<DP, ALB><<<grid_q, block, 0, side_stream>>>(        \
+        (const short*)q, (const short*)k, (const short*)v,                 \
+        (const short*)dout, lse, delta_ws, (short*)dq, (int)H, (int)S,     \
+        (int)Skv, (int)D, scale, causal, alibi, st);                       \
+    attn_bwd_dkv_kernel<DP, ALB><<<grid_kv, block, 0, stream>>>(           \
+        (const short*)q, (const short*)k, (const short*)v,                 \
+        (const short*)dout, lse, delta_ws, (short*)dk, (short*)dv, (int)H, \
+        (int)S, (int)Skv, (int)D, scale, causal, alibi, st);               \
   } while (0)
-#define LAUNCH_BWD(DP)                                                       \
-  do {                                                                       \
-    if (alibi) LAUNCH_BWD_T(DP, true, alibi);                                \
-    else LAUNCH_BWD_T(DP, false, nullptr);                                   \
+#define LAUNCH_BWD(DP)                                                     \
+  do {                                                                     \
+    if (alibi) LAUNCH_BWD_T(DP, true);                                     \
+    else LAUNCH_BWD_T(DP, false);                                          \
   } while (0)
   if (D <= 64) {
     LAUNCH_BWD(64);
   } else if (D <= 96) {
     LAUNCH_BWD(96);
-  } else if (D <= 128) {
-    LAUNCH_BWD(128);
   } else {
-    return hipErrorInvalidValue;
+    LAUNCH_BWD(128);
   }
 #undef LAUNCH_BWD
+#undef LAUNCH_BWD_T
   hipEventRecord(ev_join, side_stream);
   hipStreamWaitEvent(stream, ev_join, 0);
   return hipGetLastError();

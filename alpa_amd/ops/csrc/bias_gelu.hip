@@ -5,6 +5,7 @@
 // bf16x8 vector loads, grid-stride, dbias via deterministic striped
 // partials + column sum.
 #include "common.h"
+#include "launchers.h"
 
 // tanh-GeLU via the sigmoid identity: 0.5x(1+tanh(z)) == x*sigmoid(2z),
 // evaluated with ONE hardware __expf instead of libm tanhf (the tanh

@@ -10,85 +10,16 @@
 
 #include <vector>
 #include <algorithm>
+#include <array>
+#include <utility>
+
+#include "launchers.h"
 
 #define HIP_OK(expr)                                                       \
   do {                                                                     \
     hipError_t _e = (expr);                                                \
     TORCH_CHECK(_e == hipSuccess, "HIP error: ", hipGetErrorString(_e));   \
   } while (0)
-
-extern "C" {
-hipError_t launch_layer_norm_fwd(const void*, const void*, const void*,
-                                 void*, float*, float*, int64_t, int64_t,
-                                 float, hipStream_t);
-hipError_t launch_layer_norm_bwd_dx(const void*, const void*, const void*,
-                                    const float*, const float*, void*,
-                                    int64_t, int64_t, hipStream_t);
-hipError_t launch_layer_norm_bwd_dwdb(const void*, const void*, const float*,
-                                      const float*, float*, float*, float*,
-                                      float*, int64_t, int64_t, int,
-                                      hipStream_t);
-hipError_t launch_add_layer_norm_fwd(const void*, const void*, const void*,
-                                     const void*, void*, void*, float*,
-                                     float*, int64_t, int64_t, float,
-                                     hipStream_t);
-hipError_t launch_add_layer_norm_bwd_dx(const void*, const void*,
-                                        const void*, const void*,
-                                        const float*, const float*, void*,
-                                        int64_t, int64_t, hipStream_t);
-hipError_t launch_bias_gelu_fwd(const void*, const void*, void*, int64_t,
-                                int64_t, hipStream_t);
-hipError_t launch_bias_gelu_bwd(const void*, const void*, const void*, void*,
-                                float*, float*, int64_t, int64_t, int,
-                                hipStream_t);
-hipError_t launch_colsum_partial(const void*, float*, int64_t, int64_t, int,
-                                 hipStream_t);
-hipError_t launch_adamw(const void*, const void*, int, float, float, float,
-                        float, float, float, int, hipStream_t);
-hipError_t launch_fp8_quantize(const void*, void*, const float*, float*,
-                               int64_t, int, hipStream_t);
-hipError_t launch_fp8_quantize_dual(const void*, void*, void*, const float*,
-                                    float*, int64_t, int64_t, int,
-                                    hipStream_t);
-hipError_t launch_skinny_gemm(const void*, const void*, float*,
-                              const void*, void*, const float*, int64_t,
-                              int64_t, int64_t, int64_t, int, int,
-                              hipStream_t);
-hipError_t launch_ce_fwd(const void*, const int64_t*, float*, float*, int64_t,
-                         int64_t, hipStream_t);
-hipError_t launch_ce_bwd(const float*, const void*, const int64_t*,
-                         const float*, void*, int64_t, int64_t, hipStream_t);
-hipError_t launch_attn_fwd(const void*, const void*, const void*, void*,
-                           float*, int64_t, int64_t, int64_t, int64_t,
-                           int64_t, float, int, const float*, const int*,
-                           const int64_t*, hipStream_t);
-hipError_t launch_attn_fwd_sbuf(const void*, const void*, const void*,
-                                void*, float*, int64_t, int64_t, int64_t,
-                                int64_t, int64_t, float, int,
-                                const int64_t*, hipStream_t);
-hipError_t launch_attn_fwd_v2(const void*, const void*, const void*, void*,
-                              float*, int64_t, int64_t, int64_t, int64_t,
-                              int64_t, float, int, const int64_t*,
-                              hipStream_t);
-hipError_t launch_mfma_probe(const void*, const void*, float*, hipStream_t);
-hipError_t launch_mfma_probe32(const void*, const void*, float*,
-                               hipStream_t);
-hipError_t launch_attn_fwd_ablate(const void*, const void*, const void*,
-                                  void*, float*, int64_t, int64_t, int64_t,
-                                  int64_t, int64_t, float, int,
-                                  const int64_t*, int, hipStream_t);
-hipError_t launch_attn_bwd_dkv_ablate(const void*, const void*,
-                                      const void*, const void*,
-                                      const float*, const float*, void*,
-                                      void*, int64_t, int64_t, int64_t,
-                                      int64_t, int64_t, float, int,
-                                      const int64_t*, int, hipStream_t);
-hipError_t launch_attn_bwd(const void*, const void*, const void*,
-                           const void*, const void*, const float*, float*,
-                           void*, void*, void*, int64_t, int64_t, int64_t,
-                           int64_t, int64_t, float, int, const float*,
-                           const int64_t*, hipStream_t);
-}
 
 namespace {
 
@@ -139,6 +70,32 @@ std::vector<at::Tensor> layer_norm_fwd(const at::Tensor& x,
   return {y, mean, rstd};
 }
 
+// dw/db tail shared by both LayerNorm backwards (x is the normalized
+// input): striped column partials on the device, then the stripe-row
+// reduction through at::sum.
+std::pair<at::Tensor, at::Tensor> layer_norm_dwdb(const at::Tensor& dy,
+                                                  const at::Tensor& x,
+                                                  const at::Tensor& mean,
+                                                  const at::Tensor& rstd,
+                                                  int64_t N, int64_t H) {
+  auto f32 = x.options().dtype(at::kFloat);
+  auto dw = at::empty({H}, f32);
+  auto db = at::empty({H}, f32);
+  const int kStripes = stripes_for(N, H);
+  auto dw_part = at::empty({kStripes, H}, f32);
+  auto db_part = at::empty({kStripes, H}, f32);
+  HIP_OK(launch_layer_norm_bwd_dwdb(
+      dy.const_data_ptr(), x.const_data_ptr(),
+      (const float*)mean.const_data_ptr(),
+      (const float*)rstd.const_data_ptr(),
+      (float*)dw_part.mutable_data_ptr(), (float*)db_part.mutable_data_ptr(),
+      (float*)dw.mutable_data_ptr(), (float*)db.mutable_data_ptr(), N, H,
+      kStripes, cur_stream()));
+  at::sum_out(dw, dw_part, {0});
+  at::sum_out(db, db_part, {0});
+  return {dw, db};
+}
+
 std::vector<at::Tensor> layer_norm_bwd(const at::Tensor& dy,
                                        const at::Tensor& x,
                                        const at::Tensor& w,
@@ -148,23 +105,11 @@ std::vector<at::Tensor> layer_norm_bwd(const at::Tensor& dy,
   int64_t H = x.size(-1);
   int64_t N = x.numel() / H;
   auto dx = at::empty_like(x);
-  auto f32 = x.options().dtype(at::kFloat);
-  auto dw = at::empty({H}, f32);
-  auto db = at::empty({H}, f32);
-  const int kStripes = stripes_for(N, H);
-  auto dw_part = at::empty({kStripes, H}, f32);
-  auto db_part = at::empty({kStripes, H}, f32);
   HIP_OK(launch_layer_norm_bwd_dx(
       dy.const_data_ptr(), x.const_data_ptr(), w.const_data_ptr(),
       (const float*)mean.const_data_ptr(), (const float*)rstd.const_data_ptr(),
       dx.mutable_data_ptr(), N, H, cur_stream()));
-  HIP_OK(launch_layer_norm_bwd_dwdb(
-      dy.const_data_ptr(), x.const_data_ptr(), (const float*)mean.const_data_ptr(),
-      (const float*)rstd.const_data_ptr(), (float*)dw_part.mutable_data_ptr(),
-      (float*)db_part.mutable_data_ptr(), (float*)dw.mutable_data_ptr(),
-      (float*)db.mutable_data_ptr(), N, H, kStripes, cur_stream()));
-  at::sum_out(dw, dw_part, {0});
-  at::sum_out(db, db_part, {0});
+  auto [dw, db] = layer_norm_dwdb(dy, x, mean, rstd, N, H);
   return {dx, dw, db};
 }
 
@@ -200,27 +145,13 @@ std::vector<at::Tensor> add_layer_norm_bwd(
   int64_t H = h.size(-1);
   int64_t N = h.numel() / H;
   auto dx = at::empty_like(h);
-  auto f32 = h.options().dtype(at::kFloat);
-  auto dw = at::empty({H}, f32);
-  auto db = at::empty({H}, f32);
-  const int kStripes = stripes_for(N, H);
-  auto dw_part = at::empty({kStripes, H}, f32);
-  auto db_part = at::empty({kStripes, H}, f32);
   const void* dhp = dh.has_value() ? dh->const_data_ptr() : nullptr;
   HIP_OK(launch_add_layer_norm_bwd_dx(
       dy.const_data_ptr(), dhp, h.const_data_ptr(), w.const_data_ptr(),
       (const float*)mean.const_data_ptr(),
       (const float*)rstd.const_data_ptr(), dx.mutable_data_ptr(), N, H,
       cur_stream()));
-  HIP_OK(launch_layer_norm_bwd_dwdb(
-      dy.const_data_ptr(), h.const_data_ptr(),
-      (const float*)mean.const_data_ptr(),
-      (const float*)rstd.const_data_ptr(),
-      (float*)dw_part.mutable_data_ptr(), (float*)db_part.mutable_data_ptr(),
-      (float*)dw.mutable_data_ptr(), (float*)db.mutable_data_ptr(), N, H,
-      kStripes, cur_stream()));
-  at::sum_out(dw, dw_part, {0});
-  at::sum_out(db, db_part, {0});
+  auto [dw, db] = layer_norm_dwdb(dy, h, mean, rstd, N, H);
   return {dx, dw, db};
 }
 
@@ -368,6 +299,16 @@ void check_bf16_strided4(const at::Tensor& t, const char* name) {
 // contiguous D — so the packed qkv layout [B, S, heads, 3*D] feeds the
 // kernel directly, with no permute/contiguous copies on the hot path.
 
+// The launchers' stride array: (batch, head, seq) strides of each 4-D
+// tensor, three entries per tensor in argument order.
+template <typename... T>
+std::array<int64_t, 3 * sizeof...(T)> bhs_strides(const T&... t) {
+  std::array<int64_t, 3 * sizeof...(T)> s;
+  int64_t* p = s.data();
+  ((*p++ = t.stride(0), *p++ = t.stride(1), *p++ = t.stride(2)), ...);
+  return s;
+}
+
 // ALiBi slopes: optional per-head fp32 device tensor [H]; nullptr = off
 static const float* alibi_ptr(const c10::optional<at::Tensor>& alibi,
                               int64_t H) {
@@ -404,72 +345,14 @@ at::Tensor attn_fwd_out(const at::Tensor& q, const at::Tensor& k,
   int64_t Skv = k.size(2);
   TORCH_CHECK(D % 16 == 0 && D <= 256, "head_dim must be <=256, mult of 16");
   TORCH_CHECK(lse.is_contiguous() && lse.numel() == B * H * S);
-  int64_t strides[12] = {q.stride(0), q.stride(1), q.stride(2),
-                         k.stride(0), k.stride(1), k.stride(2),
-                         v.stride(0), v.stride(1), v.stride(2),
-                         o.stride(0), o.stride(1), o.stride(2)};
+  const auto strides = bhs_strides(q, k, v, o);
   HIP_OK(launch_attn_fwd(q.const_data_ptr(), k.const_data_ptr(),
                          v.const_data_ptr(), o.mutable_data_ptr(),
                          (float*)lse.mutable_data_ptr(), B, H, S, Skv, D,
                          (float)scale, causal ? 1 : 0, alibi_ptr(alibi, H),
-                         kv_lens_ptr(kv_lens, B), strides, cur_stream()));
+                         kv_lens_ptr(kv_lens, B), strides.data(),
+                         cur_stream()));
   return o;
-}
-
-at::Tensor attn_fwd_ablate(const at::Tensor& q, const at::Tensor& k,
-                           const at::Tensor& v, bool causal, double scale,
-                           int64_t abl) {
-  int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-  auto o = at::empty_like(q);
-  auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
-  int64_t strides[12] = {q.stride(0), q.stride(1), q.stride(2),
-                         k.stride(0), k.stride(1), k.stride(2),
-                         v.stride(0), v.stride(1), v.stride(2),
-                         o.stride(0), o.stride(1), o.stride(2)};
-  HIP_OK(launch_attn_fwd_ablate(q.const_data_ptr(), k.const_data_ptr(),
-                                v.const_data_ptr(), o.mutable_data_ptr(),
-                                (float*)lse.mutable_data_ptr(), B, H, S,
-                                k.size(2), D, (float)scale, causal ? 1 : 0,
-                                strides, (int)abl, cur_stream()));
-  return o;
-}
-
-std::vector<at::Tensor> attn_fwd_sbuf(const at::Tensor& q,
-                                      const at::Tensor& k,
-                                      const at::Tensor& v, bool causal,
-                                      double scale) {
-  int64_t B = q.size(0), H = q.size(1), S = q.size(2);
-  auto o = at::empty_like(q.contiguous());
-  auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
-  int64_t strides[12] = {q.stride(0), q.stride(1), q.stride(2),
-                         k.stride(0), k.stride(1), k.stride(2),
-                         v.stride(0), v.stride(1), v.stride(2),
-                         o.stride(0), o.stride(1), o.stride(2)};
-  HIP_OK(launch_attn_fwd_sbuf(q.const_data_ptr(), k.const_data_ptr(),
-                              v.const_data_ptr(), o.mutable_data_ptr(),
-                              (float*)lse.mutable_data_ptr(), B, H, S,
-                              k.size(2), q.size(3), (float)scale,
-                              causal ? 1 : 0, strides, cur_stream()));
-  return {o, lse};
-}
-
-std::vector<at::Tensor> attn_fwd_v2(const at::Tensor& q,
-                                    const at::Tensor& k,
-                                    const at::Tensor& v, bool causal,
-                                    double scale) {
-  int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-  auto o = at::empty_like(q.contiguous());
-  auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
-  int64_t strides[12] = {q.stride(0), q.stride(1), q.stride(2),
-                         k.stride(0), k.stride(1), k.stride(2),
-                         v.stride(0), v.stride(1), v.stride(2),
-                         o.stride(0), o.stride(1), o.stride(2)};
-  HIP_OK(launch_attn_fwd_v2(q.const_data_ptr(), k.const_data_ptr(),
-                            v.const_data_ptr(), o.mutable_data_ptr(),
-                            (float*)lse.mutable_data_ptr(), B, H, S,
-                            k.size(2), D, (float)scale, causal ? 1 : 0,
-                            strides, cur_stream()));
-  return {o, lse};
 }
 
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
@@ -584,15 +467,7 @@ void attn_bwd_out(const at::Tensor& dout, const at::Tensor& q,
   int64_t Skv = k.size(2);
   auto delta = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   auto lse_c = lse.contiguous();
-  int64_t strides[24] = {
-      q.stride(0), q.stride(1), q.stride(2),
-      k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2),
-      dout.stride(0), dout.stride(1), dout.stride(2),
-      dq.stride(0), dq.stride(1), dq.stride(2),
-      dk.stride(0), dk.stride(1), dk.stride(2),
-      dv.stride(0), dv.stride(1), dv.stride(2),
-      o.stride(0), o.stride(1), o.stride(2)};
+  const auto strides = bhs_strides(q, k, v, dout, dq, dk, dv, o);
   HIP_OK(launch_attn_bwd(q.const_data_ptr(), k.const_data_ptr(),
                          v.const_data_ptr(), o.const_data_ptr(),
                          dout.const_data_ptr(),
@@ -601,7 +476,7 @@ void attn_bwd_out(const at::Tensor& dout, const at::Tensor& q,
                          dq.mutable_data_ptr(), dk.mutable_data_ptr(),
                          dv.mutable_data_ptr(), B, H, S, Skv, D,
                          (float)scale, causal ? 1 : 0, alibi_ptr(alibi, H),
-                         strides, cur_stream()));
+                         strides.data(), cur_stream()));
 }
 
 std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
@@ -615,28 +490,6 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
   auto dv = at::empty_like(v.contiguous());
   attn_bwd_out(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, alibi);
   return {dq, dk, dv};
-}
-
-void attn_bwd_dkv_ablate(const at::Tensor& dout, const at::Tensor& q,
-                         const at::Tensor& k, const at::Tensor& v,
-                         const at::Tensor& lse, const at::Tensor& delta,
-                         at::Tensor dk, at::Tensor dv, bool causal,
-                         double scale, int64_t abl) {
-  int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-  int64_t strides[24] = {
-      q.stride(0), q.stride(1), q.stride(2),
-      k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2),
-      dout.stride(0), dout.stride(1), dout.stride(2),
-      0, 0, 0,
-      dk.stride(0), dk.stride(1), dk.stride(2),
-      dv.stride(0), dv.stride(1), dv.stride(2), 0, 0, 0};
-  HIP_OK(launch_attn_bwd_dkv_ablate(
-      q.const_data_ptr(), k.const_data_ptr(), v.const_data_ptr(),
-      dout.const_data_ptr(), (const float*)lse.const_data_ptr(),
-      (const float*)delta.const_data_ptr(), dk.mutable_data_ptr(),
-      dv.mutable_data_ptr(), B, H, S, k.size(2), D, (float)scale,
-      causal ? 1 : 0, strides, (int)abl, cur_stream()));
 }
 
 at::Tensor mfma_probe(const at::Tensor& a, const at::Tensor& b) {
@@ -655,8 +508,6 @@ at::Tensor mfma_probe32(const at::Tensor& a, const at::Tensor& b) {
   return d;
 }
 
-}  // namespace
-
 // fp8 quantize: one-pass amax + delayed-scale cast (optional transposed
 // twin for the dW GEMM).  x: bf16 contiguous; scale: fp32 scalar tensor
 // on device (previous-step scale); returns (q, qt | empty, amax).
@@ -668,7 +519,6 @@ std::vector<at::Tensor> fp8_quantize(const at::Tensor& x,
   TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat &&
               scale.numel() == 1, "scale must be a device fp32 scalar");
   auto qtype = e5m2 ? at::kFloat8_e5m2 : at::kFloat8_e4m3fn;
-  auto stream = c10::hip::getCurrentHIPStream().stream();
   auto amax = at::zeros({1}, x.options().dtype(at::kFloat));
   auto q = at::empty(x.sizes(), x.options().dtype(qtype));
   if (!dual) {
@@ -676,7 +526,7 @@ std::vector<at::Tensor> fp8_quantize(const at::Tensor& x,
     HIP_OK(launch_fp8_quantize(x.const_data_ptr(), q.data_ptr(),
                                (const float*)scale.const_data_ptr(),
                                (float*)amax.data_ptr(), x.numel(),
-                               e5m2 ? 1 : 0, stream));
+                               e5m2 ? 1 : 0, cur_stream()));
     return {q, at::Tensor(), amax};
   }
   TORCH_CHECK(x.dim() == 2, "dual quantize needs a 2-D tensor");
@@ -686,14 +536,18 @@ std::vector<at::Tensor> fp8_quantize(const at::Tensor& x,
                                   qt.data_ptr(),
                                   (const float*)scale.const_data_ptr(),
                                   (float*)amax.data_ptr(), M, N,
-                                  e5m2 ? 1 : 0, stream));
+                                  e5m2 ? 1 : 0, cur_stream()));
   return {q, qt, amax};
 }
+
+}  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // Bump when the Python<->extension call surface changes; checked by
   // alpa_amd/version.py (reference check_alpa_jaxlib_version, version.py:10)
-  m.attr("ABI_VERSION") = 2;  // r2: fp8_quantize, NT-templated attention
+  // 3: the experimental attention entries (attn_fwd_v2, attn_fwd_sbuf,
+  // attn_fwd_ablate, attn_bwd_dkv_ablate) were removed
+  m.attr("ABI_VERSION") = 3;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)");
   m.def("add_layer_norm_fwd", &add_layer_norm_fwd,
@@ -718,11 +572,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("causal"), py::arg("scale"),
         py::arg("alibi") = py::none(), py::arg("kv_lens") = py::none());
-  m.def("attn_fwd_v2", &attn_fwd_v2, "32x32-MFMA fwd experiment");
-  m.def("attn_fwd_ablate", &attn_fwd_ablate, "ablation variants (perf)");
-  m.def("attn_bwd_dkv_ablate", &attn_bwd_dkv_ablate, "dkv ablation (perf)");
-  m.def("attn_fwd_sbuf", &attn_fwd_sbuf,
-        "single-buffer LDS fwd variant (2 blocks/CU experiment)");
   m.def("attn_fwd_blocked", &attn_fwd_blocked,
         "blocked fwd for head_dim > 128 (hipBLASLt scores)");
   m.def("attn_bwd", &attn_bwd, "flash attention bwd (gfx950 MFMA)",

@@ -5,6 +5,7 @@
 // materializes a softmax tensor).  Backward: dlogits = (softmax - onehot)
 // * dloss recomputed from (logits, lse).
 #include "common.h"
+#include "launchers.h"
 
 #define CE_BLOCK 256
 

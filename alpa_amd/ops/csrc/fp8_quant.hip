@@ -12,6 +12,7 @@
 // while the CURRENT amax is reduced into `amax_out` via atomicMax on
 // positive-float bits.
 #include "common.h"
+#include "launchers.h"
 
 // e4m3: clamp 448; e5m2 (ISA name bf8): clamp 57344. RNE conversion via
 // the packed hardware converters.

@@ -1,0 +1,103 @@
+// Prototypes of every extern "C" kernel launcher in the library.
+//
+// Included by each *.hip that defines launchers and by bindings.cpp that
+// calls them.  C linkage forbids overloads, so a definition whose parameter
+// types or order drift from this header is a compile error instead of a
+// clean link that corrupts memory at run time.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+extern "C" {
+
+// ---- layernorm.hip ----
+hipError_t launch_layer_norm_fwd(const void* x, const void* w, const void* b,
+                                 void* y, float* mean, float* rstd, int64_t N,
+                                 int64_t H, float eps, hipStream_t stream);
+hipError_t launch_layer_norm_bwd_dx(const void* dy, const void* x,
+                                    const void* w, const float* mean,
+                                    const float* rstd, void* dx, int64_t N,
+                                    int64_t H, hipStream_t stream);
+hipError_t launch_layer_norm_bwd_dwdb(const void* dy, const void* x,
+                                      const float* mean, const float* rstd,
+                                      float* dw_part, float* db_part,
+                                      float* dw, float* db, int64_t N,
+                                      int64_t H, int P, hipStream_t stream);
+hipError_t launch_add_layer_norm_fwd(const void* a, const void* b,
+                                     const void* w, const void* bias,
+                                     void* h, void* y, float* mean,
+                                     float* rstd, int64_t N, int64_t H,
+                                     float eps, hipStream_t stream);
+hipError_t launch_add_layer_norm_bwd_dx(const void* dy, const void* dh,
+                                        const void* x, const void* w,
+                                        const float* mean, const float* rstd,
+                                        void* dx, int64_t N, int64_t H,
+                                        hipStream_t stream);
+
+// ---- bias_gelu.hip ----
+hipError_t launch_bias_gelu_fwd(const void* x, const void* bias, void* y,
+                                int64_t N, int64_t F, hipStream_t stream);
+hipError_t launch_bias_gelu_bwd(const void* dy, const void* x,
+                                const void* bias, void* dx, float* db_part,
+                                float* db, int64_t N, int64_t F, int P,
+                                hipStream_t stream);
+hipError_t launch_colsum_partial(const void* t, float* part, int64_t N,
+                                 int64_t F, int P, hipStream_t stream);
+
+// ---- adamw.hip ----
+hipError_t launch_adamw(const void* descs_dev, const void* chunks_dev,
+                        int num_chunks, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, float grad_scale,
+                        int step, hipStream_t stream);
+
+// ---- fp8_quant.hip ----
+hipError_t launch_fp8_quantize(const void* src, void* q, const float* scale,
+                               float* amax, int64_t total, int e5m2,
+                               hipStream_t stream);
+hipError_t launch_fp8_quantize_dual(const void* src, void* q, void* qt,
+                                    const float* scale, float* amax,
+                                    int64_t M, int64_t N, int e5m2,
+                                    hipStream_t stream);
+
+// ---- skinny_gemm.hip ----
+hipError_t launch_skinny_gemm(const void* wp, const void* x, float* part,
+                              const void* bias_or_null, void* y,
+                              const float* wscale_or_null, int64_t M,
+                              int64_t MT, int64_t N, int64_t K, int splits,
+                              int fp8, hipStream_t stream);
+
+// ---- cross_entropy.hip ----
+hipError_t launch_ce_fwd(const void* logits, const int64_t* targets,
+                         float* loss, float* lse, int64_t N, int64_t V,
+                         hipStream_t stream);
+hipError_t launch_ce_bwd(const float* dloss, const void* logits,
+                         const int64_t* targets, const float* lse,
+                         void* dlogits, int64_t N, int64_t V,
+                         hipStream_t stream);
+
+// ---- attention.hip ----
+// strides: q(3) k(3) v(3) o(3), each (batch, head, seq) in elements
+hipError_t launch_attn_fwd(const void* q, const void* k, const void* v,
+                           void* o, float* lse, int64_t B, int64_t H,
+                           int64_t S, int64_t Skv, int64_t D, float scale,
+                           int causal, const float* alibi,
+                           const int* kv_lens, const int64_t* strides,
+                           hipStream_t stream);
+// strides: q(3) k(3) v(3) do(3) dq(3) dk(3) dv(3) o(3)
+hipError_t launch_attn_bwd(const void* q, const void* k, const void* v,
+                           const void* o, const void* dout,
+                           const float* lse, float* delta_ws, void* dq,
+                           void* dk, void* dv, int64_t B, int64_t H,
+                           int64_t S, int64_t Skv, int64_t D, float scale,
+                           int causal, const float* alibi,
+                           const int64_t* strides, hipStream_t stream);
+
+// ---- mfma_probe.hip ----
+hipError_t launch_mfma_probe(const void* a, const void* b, float* d,
+                             hipStream_t stream);
+hipError_t launch_mfma_probe32(const void* a, const void* b, float* d,
+                               hipStream_t stream);
+
+}  // extern "C"

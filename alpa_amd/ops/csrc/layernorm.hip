@@ -8,6 +8,7 @@
 // Covers the reference's LayerNorm fwd/bwd fusion slot (SURVEY.md §2.3
 // kernel table: "LayerNorm fwd/bwd | elementwise+reduce fusion | [B·S, H]").
 #include "common.h"
+#include "launchers.h"
 
 #define LN_BLOCK 256
 

@@ -36,6 +36,7 @@
 // (see ops/__init__.py _skinny_splits) to fill the 256 CUs AND bound
 // the LDS slice; K % (8*S) == 0, N % 64 == 0, rounds % 8 == 0.
 #include "common.h"
+#include "launchers.h"
 
 typedef unsigned char u8x8 __attribute__((ext_vector_type(8)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));

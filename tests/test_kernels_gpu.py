@@ -557,6 +557,28 @@ def test_attention_fwd_blocked_d256(ext):
     torch.testing.assert_close(o.float(), o_r, rtol=2e-2, atol=2e-2)
 
 
+@pytest.mark.parametrize("causal", [True, False])
+@pytest.mark.parametrize("S,D", [(192, 256), (192, 160)])
+def test_attention_fwd_fused_d256(ext, causal, S, D):
+    """The fused single-buffered Dp=256 forward (head_dim in (128, 256]).
+    S=192 is one full 128-row block plus a ragged one over three 64-wide
+    kv tiles; D=160 exercises the head-dim guards inside Dp=256.  Same
+    bounds as test_attention_fwd: both kernels accumulate scores in fp32
+    from the same bf16 inputs."""
+    torch.manual_seed(19)
+    B, Hh = 1, 2
+    q = torch.randn(B, Hh, S, D, device="cuda", dtype=torch.bfloat16)
+    k = torch.randn(B, Hh, S, D, device="cuda", dtype=torch.bfloat16)
+    v = torch.randn(B, Hh, S, D, device="cuda", dtype=torch.bfloat16)
+    scale = 1.0 / math.sqrt(D)
+    o, lse = ext.attn_fwd(q, k, v, causal, scale)
+    o_ref, lse_ref = ref.attention_fwd(q.float(), k.float(), v.float(),
+                                       causal, scale)
+    torch.testing.assert_close(o.float(), o_ref, rtol=2e-2, atol=2e-2)
+    torch.testing.assert_close(lse.view(-1), lse_ref.view(-1), rtol=1e-3,
+                               atol=1e-3)
+
+
 def test_codegen_6b_heads_on_gpu():
     """A CodeGen-6B-shaped decoder (head_dim 256) generates end-to-end
     through the blocked attention path."""
