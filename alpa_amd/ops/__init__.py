@@ -391,8 +391,13 @@ _ADAM_TABLE_CACHE: dict = {}
 def _adam_tables(params, grads, exp_avgs, exp_avg_sqs):
     """Build (and cache) the device-side tensor-descriptor + chunk tables
     consumed by the multi-tensor AdamW kernel (one launch per step)."""
-    key = tuple(p.data_ptr() for p in params) + \
-        tuple(g.data_ptr() for g in grads)
+    # the key covers every field a descriptor row holds: a second optimizer
+    # over the same params brings new moment buffers, and the caching
+    # allocator can hand the same base pointers to tensors of another
+    # size or dtype
+    key = tuple((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                 p.numel(), p.dtype)
+                for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs))
     hit = _ADAM_TABLE_CACHE.get(key)
     if hit is not None:
         return hit

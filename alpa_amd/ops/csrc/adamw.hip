@@ -40,11 +40,39 @@ __global__ void adamw_kernel(const AdamTensorDesc* __restrict__ descs,
   int64_t end = min(base + ADAM_CHUNK, d.numel);
 
   const float wd_factor = 1.0f - lr * weight_decay;
-  // vectorized main loop: 8 elements/thread/iteration (G13 — the r1
-  // scalar kernel ran 2x off the HBM roofline on 2-byte accesses);
-  // torch allocations are 256B-aligned and chunk bases are multiples
-  // of ADAM_CHUNK, so 16B vector access is aligned
-  const int64_t n_full = (end - base) / 8 * 8;
+  // one element, all dtypes: the tail after the vector loop, and every
+  // element of a tensor that cannot take the vector loop
+  auto scalar_update = [&](int64_t i) {
+    float g, p;
+    if (d.is_bf16) {
+      g = bf2f(((const short*)d.g)[i]) * grad_scale;
+      p = bf2f(((const short*)d.p)[i]);
+    } else {
+      g = ((const float*)d.g)[i] * grad_scale;
+      p = ((const float*)d.p)[i];
+    }
+    float m = d.m[i] = d.m[i] * beta1 + g * (1.0f - beta1);
+    float v = d.v[i] = d.v[i] * beta2 + g * g * (1.0f - beta2);
+    p = p * wd_factor;
+    p -= lr * (m / bc1) / (sqrtf(v / bc2) + eps);
+    if (d.is_bf16)
+      ((short*)d.p)[i] = f2bf(p);
+    else
+      ((float*)d.p)[i] = p;
+  };
+
+  // The vector loop moves 16 B per access and needs all four streams
+  // 16B-aligned (chunk bases are multiples of ADAM_CHUNK and keep the
+  // phase).  Whole torch allocations are, but a tensor may be a view at
+  // any element offset: a ZeRO-2 shard is flat[rank * shard_n:] with
+  // shard_n any integer, and a bucket's grad views start at the summed
+  // numel of the params before them.  Such a tensor is updated element by
+  // element: correct, at the 2-byte-access rate the vector loop was
+  // written to avoid (the r1 scalar kernel ran 2x off the HBM roofline).
+  const bool vec = ((((uintptr_t)d.p) | ((uintptr_t)d.g) | ((uintptr_t)d.m) |
+                     ((uintptr_t)d.v)) & 15) == 0;
+  // vectorized main loop: 8 elements/thread/iteration (G13)
+  const int64_t n_full = vec ? (end - base) / 8 * 8 : 0;
   for (int64_t i = base + (int64_t)threadIdx.x * 8; i < base + n_full;
        i += (int64_t)ADAM_BLOCK * 8) {
     float g[8], p[8];
@@ -98,24 +126,8 @@ __global__ void adamw_kernel(const AdamTensorDesc* __restrict__ descs,
     }
   }
   // scalar tail (final partial 8-group of the tensor's last chunk)
-  for (int64_t i = base + n_full + threadIdx.x; i < end; i += ADAM_BLOCK) {
-    float g, p;
-    if (d.is_bf16) {
-      g = bf2f(((const short*)d.g)[i]) * grad_scale;
-      p = bf2f(((const short*)d.p)[i]);
-    } else {
-      g = ((const float*)d.g)[i] * grad_scale;
-      p = ((const float*)d.p)[i];
-    }
-    float m = d.m[i] = d.m[i] * beta1 + g * (1.0f - beta1);
-    float v = d.v[i] = d.v[i] * beta2 + g * g * (1.0f - beta2);
-    p = p * wd_factor;
-    p -= lr * (m / bc1) / (sqrtf(v / bc2) + eps);
-    if (d.is_bf16)
-      ((short*)d.p)[i] = f2bf(p);
-    else
-      ((float*)d.p)[i] = p;
-  }
+  for (int64_t i = base + n_full + threadIdx.x; i < end; i += ADAM_BLOCK)
+    scalar_update(i);
 }
 
 extern "C" {

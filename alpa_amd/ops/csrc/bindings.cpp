@@ -33,6 +33,30 @@ void check_bf16_contig(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// per-feature vector (LayerNorm weight/bias, GeLU bias): bf16 [n]; the
+// kernels read it with 16-byte loads straight off the raw pointer
+void check_bf16_vec(const at::Tensor& t, const char* name, int64_t n) {
+  check_bf16_contig(t, name);
+  TORCH_CHECK(t.numel() == n, name, " must have ", n, " elements, got ",
+              t.numel());
+}
+
+// saved per-row statistics: fp32 [N]
+void check_row_stats(const at::Tensor& t, const char* name, int64_t N) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be fp32");
+  TORCH_CHECK(t.is_contiguous() && t.numel() == N, name,
+              " must be contiguous [N]");
+}
+
+// a second [.., H] operand that the kernel indexes exactly like `ref`
+void check_same_shape(const at::Tensor& t, const char* name,
+                      const at::Tensor& ref, const char* ref_name) {
+  check_bf16_contig(t, name);
+  TORCH_CHECK(t.sizes() == ref.sizes(), name, " must have the shape of ",
+              ref_name);
+}
+
 // Deterministic column-partial stripe count: enough (stripes x col-chunks)
 // blocks to fill 256 CUs, bounded by the row count.
 int stripes_for(int64_t N, int64_t cols) {
@@ -58,6 +82,8 @@ std::vector<at::Tensor> layer_norm_fwd(const at::Tensor& x,
   int64_t H = x.size(-1);
   int64_t N = x.numel() / H;
   TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
+  check_bf16_vec(w, "w", H);
+  check_bf16_vec(b, "b", H);
   auto y = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
   auto mean = at::empty({N}, f32);
@@ -101,9 +127,14 @@ std::vector<at::Tensor> layer_norm_bwd(const at::Tensor& dy,
                                        const at::Tensor& w,
                                        const at::Tensor& mean,
                                        const at::Tensor& rstd) {
-  check_bf16_contig(dy, "dy");
+  check_bf16_contig(x, "x");
+  check_same_shape(dy, "dy", x, "x");
   int64_t H = x.size(-1);
   int64_t N = x.numel() / H;
+  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
+  check_bf16_vec(w, "w", H);
+  check_row_stats(mean, "mean", N);
+  check_row_stats(rstd, "rstd", N);
   auto dx = at::empty_like(x);
   HIP_OK(launch_layer_norm_bwd_dx(
       dy.const_data_ptr(), x.const_data_ptr(), w.const_data_ptr(),
@@ -123,6 +154,10 @@ std::vector<at::Tensor> add_layer_norm_fwd(const at::Tensor& a,
   check_bf16_contig(a, "a");
   int64_t H = a.size(-1);
   int64_t N = a.numel() / H;
+  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
+  if (b.has_value()) check_same_shape(*b, "b", a, "a");
+  check_bf16_vec(w, "w", H);
+  check_bf16_vec(bias, "bias", H);
   auto h = at::empty_like(a);
   auto y = at::empty_like(a);
   auto f32 = a.options().dtype(at::kFloat);
@@ -141,9 +176,15 @@ std::vector<at::Tensor> add_layer_norm_bwd(
     const at::Tensor& dy, const c10::optional<at::Tensor>& dh,
     const at::Tensor& h, const at::Tensor& w, const at::Tensor& mean,
     const at::Tensor& rstd) {
-  check_bf16_contig(dy, "dy");
+  check_bf16_contig(h, "h");
+  check_same_shape(dy, "dy", h, "h");
+  if (dh.has_value()) check_same_shape(*dh, "dh", h, "h");
   int64_t H = h.size(-1);
   int64_t N = h.numel() / H;
+  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
+  check_bf16_vec(w, "w", H);
+  check_row_stats(mean, "mean", N);
+  check_row_stats(rstd, "rstd", N);
   auto dx = at::empty_like(h);
   const void* dhp = dh.has_value() ? dh->const_data_ptr() : nullptr;
   HIP_OK(launch_add_layer_norm_bwd_dx(
@@ -162,6 +203,7 @@ at::Tensor bias_gelu_fwd(const at::Tensor& x, const at::Tensor& bias) {
   int64_t F = x.size(-1);
   int64_t N = x.numel() / F;
   TORCH_CHECK(F % 8 == 0, "F must be a multiple of 8");
+  check_bf16_vec(bias, "bias", F);
   auto y = at::empty_like(x);
   HIP_OK(launch_bias_gelu_fwd(x.const_data_ptr(), bias.const_data_ptr(),
                               y.mutable_data_ptr(), N, F, cur_stream()));
@@ -171,9 +213,12 @@ at::Tensor bias_gelu_fwd(const at::Tensor& x, const at::Tensor& bias) {
 std::vector<at::Tensor> bias_gelu_bwd(const at::Tensor& dy,
                                       const at::Tensor& x,
                                       const at::Tensor& bias) {
-  check_bf16_contig(dy, "dy");
+  check_bf16_contig(x, "x");
+  check_same_shape(dy, "dy", x, "x");
   int64_t F = x.size(-1);
   int64_t N = x.numel() / F;
+  TORCH_CHECK(F % 8 == 0, "F must be a multiple of 8");
+  check_bf16_vec(bias, "bias", F);
   auto dx = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
   const int kStripes = stripes_for_vec8(N, F);

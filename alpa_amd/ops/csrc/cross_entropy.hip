@@ -28,12 +28,15 @@ __global__ void ce_fwd_kernel(const short* __restrict__ logits,
         s *= __expf(m - f);
         m = f;
       }
-      s += __expf(f - m);
+      // a -inf logit (masked vocab slot) adds nothing; while m is still
+      // -inf, f - m would be inf - inf = NaN
+      if (f != -INFINITY) s += __expf(f - m);
     }
   }
-  // combine across block: need global max first
+  // combine across block: need global max first.  A thread that saw
+  // nothing finite (or no element at all) still has m = -inf and s = 0.
   float gm = block_reduce_max(m, red);
-  s *= __expf(m - gm);
+  s = (m == -INFINITY) ? 0.f : s * __expf(m - gm);
   float gs = block_reduce_sum(s, red);
   float lse = gm + __logf(gs);
   if (threadIdx.x == 0) {

@@ -26,28 +26,34 @@ __global__ void layer_norm_fwd_kernel(const short* __restrict__ x,
   short* yr = y + (int64_t)row * H;
   __shared__ float red[LN_BLOCK / 64];
 
-  // pass 1: sum & sumsq (vectorized)
-  float s = 0.f, ss = 0.f;
+  // pass 1: mean (vectorized)
+  float s = 0.f;
+  for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
+    bf16x8 v = *reinterpret_cast<const bf16x8*>(xr + i);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += bf2f(v[j]);
+  }
+  const float mean = block_reduce_sum(s, red) / H;
+  // pass 2: variance as the mean of squared deviations.  The one-pass
+  // E[x^2] - mean^2 form cancels catastrophically once |mean| >> std
+  // (a near-constant row came out with a negative variance, so NaN).
+  // The row was just read, so this pass hits L2.
+  float ss = 0.f;
   for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
     bf16x8 v = *reinterpret_cast<const bf16x8*>(xr + i);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float f = bf2f(v[j]);
-      s += f;
-      ss += f * f;
+      float d = bf2f(v[j]) - mean;
+      ss += d * d;
     }
   }
-  s = block_reduce_sum(s, red);
-  ss = block_reduce_sum(ss, red);
-  const float mean = s / H;
-  const float var = ss / H - mean * mean;
-  const float rstd = rsqrtf(var + eps);
+  const float rstd = rsqrtf(block_reduce_sum(ss, red) / H + eps);
   if (threadIdx.x == 0) {
     mean_out[row] = mean;
     rstd_out[row] = rstd;
   }
 
-  // pass 2: normalize (x re-read hits L2/L3)
+  // pass 3: normalize (x re-read hits L2/L3)
   for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
     bf16x8 v = *reinterpret_cast<const bf16x8*>(xr + i);
     bf16x8 wv = *reinterpret_cast<const bf16x8*>(w + i);
@@ -229,7 +235,9 @@ __global__ void add_layer_norm_fwd_kernel(const short* __restrict__ a,
   short* yr = y + (int64_t)row * H;
   __shared__ float red[LN_BLOCK / 64];
 
-  float s = 0.f, ss = 0.f;
+  // statistics are those of the ROUNDED h: that is the tensor the
+  // normalize pass, the backward and every later layer see
+  float s = 0.f;
   for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
     bf16x8 av = *reinterpret_cast<const bf16x8*>(ar + i);
     bf16x8 hv;
@@ -237,26 +245,31 @@ __global__ void add_layer_norm_fwd_kernel(const short* __restrict__ a,
       bf16x8 bv = *reinterpret_cast<const bf16x8*>(br + i);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float f = bf2f(av[j]) + bf2f(bv[j]);
-        hv[j] = f2bf(f);
-        s += f;
-        ss += f * f;
+        hv[j] = f2bf(bf2f(av[j]) + bf2f(bv[j]));
+        s += bf2f(hv[j]);
       }
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float f = bf2f(av[j]);
         hv[j] = av[j];
-        s += f;
-        ss += f * f;
+        s += bf2f(av[j]);
       }
     }
     *reinterpret_cast<bf16x8*>(hr + i) = hv;
   }
-  s = block_reduce_sum(s, red);
-  ss = block_reduce_sum(ss, red);
-  const float mean = s / H;
-  const float rstd = rsqrtf(ss / H - mean * mean + eps);
+  const float mean = block_reduce_sum(s, red) / H;
+  // two-pass variance (see layer_norm_fwd_kernel); each thread re-reads
+  // the h elements it wrote itself, so no fence is needed
+  float ss = 0.f;
+  for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
+    bf16x8 hv = *reinterpret_cast<const bf16x8*>(hr + i);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float d = bf2f(hv[j]) - mean;
+      ss += d * d;
+    }
+  }
+  const float rstd = rsqrtf(block_reduce_sum(ss, red) / H + eps);
   if (threadIdx.x == 0) {
     mean_out[row] = mean;
     rstd_out[row] = rstd;

@@ -1,0 +1,609 @@
+"""Edge shapes and hostile values for the row and elementwise gfx950 kernels.
+
+tests/test_kernels_gpu.py runs each of these kernels at one friendly shape
+on unit normals.  Here the same kernels meet vector-width tails, partial
+stripes, grid-stride wraps, chunk boundaries, near-constant rows, -inf
+logits and saturating values.  The oracle is alpa_amd.ops.reference on
+fp64 copies of the bf16 inputs.
+"""
+import math
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from alpa_amd.ops import reference as ref
+
+BF16 = torch.bfloat16
+EPS = 1e-5
+
+
+@pytest.fixture(scope="module")
+def ext():
+    from alpa_amd.ops._backend import hip_ops
+    e = hip_ops()
+    assert e is not None, "HIP extension must be built on a GPU box"
+    return e
+
+
+def _randn_bf16(gen, *shape):
+    """Seeded CPU normals, rounded to bf16, on the GPU."""
+    return torch.randn(*shape, generator=gen).to(BF16).cuda()
+
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _assert_colsum(got, terms64, name, extra=None):
+    """Per column: |got - sum64| <= 1e-4 * sum_rows|term| + 1e-6 (+ extra).
+
+    Derived, not measured: fp32 sequential accumulation of n terms is off
+    by at most n*u*sum|t|; n <= 513 and u = 6e-8 give 3.1e-5, rounded up
+    to 1e-4.  A missing or doubled row moves a column by |t_row| ~ 1,
+    far outside this."""
+    want = terms64.sum(0)
+    bound = 1e-4 * terms64.abs().sum(0) + 1e-6
+    if extra is not None:
+        bound = bound + extra
+    err = (got.double() - want).abs()
+    worst = (err / bound).max().item()
+    print(f"{name}: worst err/bound = {worst:.3g}")
+    assert worst <= 1.0, (name, worst)
+
+
+# ----------------------------------------------------------- LayerNorm shapes
+
+# H: one thread only / < 2048 so some threads idle / thread 0 takes a
+# second trip / the model size.  N: P = N < 64 / 70 / 513 not divisible by
+# the stripe count.  (70, 8192) is the one shape where the stripe count
+# bottoms out at 64, so N = 70 splits into stripes of one and two rows.
+LN_SHAPES = [(N, H) for H in (8, 1000, 2056, 2560) for N in (1, 3, 70, 513)]
+LN_SHAPES.append((70, 8192))
+
+
+def _ln_inputs(N, H, seed):
+    g = _gen(seed)
+    return (_randn_bf16(g, N, H), _randn_bf16(g, H), _randn_bf16(g, H),
+            _randn_bf16(g, N, H))
+
+
+def _check_ln_fwd(y, mean, rstd, x64, w64, b64):
+    y64, mean64, rstd64 = ref.layer_norm_fwd(x64, w64, b64, EPS)
+    torch.testing.assert_close(mean.double(), mean64, rtol=1e-3, atol=1e-3)
+    torch.testing.assert_close(rstd.double(), rstd64, rtol=1e-3, atol=1e-3)
+    torch.testing.assert_close(y.double(), y64, rtol=2e-2, atol=2e-2)
+    return mean64.float(), rstd64.float()
+
+
+def _check_ln_bwd(dx, dw, db, dy, x64, w64, mean32, rstd32, dh64=None):
+    dy64 = dy.double()
+    # the kernel was fed the fp32 statistics; the oracle uses the same
+    mean64, rstd64 = mean32.double(), rstd32.double()
+    dx64, _, _ = ref.layer_norm_bwd(dy64, x64, w64, mean64, rstd64)
+    if dh64 is not None:
+        dx64 = dx64 + dh64
+    torch.testing.assert_close(dx.double(), dx64, rtol=3e-2, atol=3e-2)
+    xhat64 = (x64 - mean64.unsqueeze(-1)) * rstd64.unsqueeze(-1)
+    _assert_colsum(dw, dy64 * xhat64, "dw")
+    _assert_colsum(db, dy64, "db")
+
+
+@pytest.mark.parametrize("N,H", LN_SHAPES)
+def test_layer_norm_shapes(ext, N, H):
+    x, w, b, dy = _ln_inputs(N, H, 100)
+    y, mean, rstd = ext.layer_norm_fwd(x, w, b, EPS)
+    mean32, rstd32 = _check_ln_fwd(y, mean, rstd, x.double(), w.double(),
+                                   b.double())
+    # reference statistics in, so forward error does not compound
+    dx, dw, db = ext.layer_norm_bwd(dy, x, w, mean32, rstd32)
+    _check_ln_bwd(dx, dw, db, dy, x.double(), w.double(), mean32, rstd32)
+
+
+@pytest.mark.parametrize("with_delta", [True, False])
+@pytest.mark.parametrize("N,H", LN_SHAPES)
+def test_add_layer_norm_shapes(ext, N, H, with_delta):
+    a, w, bias, dy = _ln_inputs(N, H, 101)
+    g = _gen(102)
+    delta = _randn_bf16(g, N, H) if with_delta else None
+    dh = _randn_bf16(g, N, H) if with_delta else None
+    h, y, mean, rstd = ext.add_layer_norm_fwd(a, delta, w, bias, EPS)
+    h64 = a.double() + (delta.double() if with_delta else 0.0)
+    torch.testing.assert_close(h.double(), h64, rtol=2e-2, atol=2e-2)
+    # one fp32 add of two bf16 values, rounded to nearest even, on both
+    # sides: the stored h is exact.  The oracle normalises this h (what
+    # backward and later layers see), computed without the kernel.
+    want_h = (a.float() + delta.float()).to(BF16) if with_delta else a
+    assert torch.equal(h, want_h)
+    hk64 = want_h.double()
+    mean32, rstd32 = _check_ln_fwd(y, mean, rstd, hk64, w.double(),
+                                   bias.double())
+    dx, dw, db = ext.add_layer_norm_bwd(dy, dh, h, w, mean32, rstd32)
+    _check_ln_bwd(dx, dw, db, dy, hk64, w.double(), mean32, rstd32,
+                  dh.double() if with_delta else None)
+
+
+# --------------------------------------------------- LayerNorm hostile values
+
+def _hostile_rows(H, seed):
+    """(base, perturbation) per row; the row is base + perturbation.  Rows
+    whose |mean| dwarfs their spread are where E[x^2] - mean^2 cancels."""
+    g = _gen(seed)
+    base = torch.zeros(6, H)
+    pert = torch.zeros(6, H)
+    base[0] = 100.5                      # exactly constant
+    base[1] = 100.5
+    pert[1, H // 3] = 0.5                # one element up one bf16 ulp
+    base[2] = 100.0
+    pert[2] = 0.1 * torch.randn(H, generator=g)
+    base[3] = 1000.0
+    pert[3] = torch.randn(H, generator=g)
+    base[4] = -300.0
+    pert[4] = 0.5 * torch.randn(H, generator=g)
+    pert[5] = torch.randn(H, generator=g)    # control
+    return base, pert
+
+
+def _check_hostile(y, mean, rstd, rows64, w64, b64):
+    for name, t in (("y", y), ("mean", mean), ("rstd", rstd)):
+        assert torch.isfinite(t).all(), f"{name} has non-finite entries"
+    y64, mean64, rstd64 = ref.layer_norm_fwd(rows64, w64, b64, EPS)
+    print("rstd got", rstd.tolist(), "want", rstd64.tolist())
+    # atol covers the fp32 rounding of a mean that is itself ~0 (control)
+    torch.testing.assert_close(mean.double(), mean64, rtol=1e-3, atol=1e-6)
+    torch.testing.assert_close(rstd.double(), rstd64, rtol=1e-3, atol=0)
+    # near-constant rows blow the bf16 input grid up by rstd; they are
+    # held by the rstd and finiteness checks above
+    tame = rstd64 < 50
+    assert tame.sum() >= 4
+    torch.testing.assert_close(y.double()[tame], y64[tame], rtol=2e-2,
+                               atol=2e-2)
+
+
+@pytest.mark.parametrize("H", [1000, 2560])
+def test_layer_norm_hostile_values(ext, H):
+    base, pert = _hostile_rows(H, 110)
+    x = (base + pert).to(BF16).cuda()
+    assert x[1].float().max().item() == 101.0 and \
+        x[1].float().min().item() == 100.5
+    g = _gen(111)
+    w, b = _randn_bf16(g, H), _randn_bf16(g, H)
+    y, mean, rstd = ext.layer_norm_fwd(x, w, b, EPS)
+    _check_hostile(y, mean, rstd, x.double(), w.double(), b.double())
+
+
+@pytest.mark.parametrize("with_delta", [True, False])
+@pytest.mark.parametrize("H", [1000, 2560])
+def test_add_layer_norm_hostile_values(ext, H, with_delta):
+    base, pert = _hostile_rows(H, 110)
+    g = _gen(111)
+    w, b = _randn_bf16(g, H), _randn_bf16(g, H)
+    if with_delta:
+        a, delta = base.to(BF16).cuda(), pert.to(BF16).cuda()
+        want_h = (a.float() + delta.float()).to(BF16)
+    else:
+        a, delta = (base + pert).to(BF16).cuda(), None
+        want_h = a
+    h, y, mean, rstd = ext.add_layer_norm_fwd(a, delta, w, b, EPS)
+    # one fp32 add of two bf16 values, rounded to nearest even, on both
+    # sides: h is exact
+    assert torch.equal(h, want_h)
+    _check_hostile(y, mean, rstd, h.double(), w.double(), b.double())
+
+
+# ------------------------------------------------------------------ bias+GeLU
+
+_GELU_SPECIALS = [0.0, -0.0, 6.0, -6.0, 30.0, -30.0, 200.0, -200.0, 1e4,
+                  -1e4]
+
+
+def _sprinkle(x, values, gen, share=0.01):
+    """Overwrite about `share` of x (at least one of each value when it
+    fits) with entries of `values`."""
+    flat = x.view(-1)
+    n = flat.numel()
+    k = min(n, max(len(values), int(n * share)))
+    idx = torch.randperm(n, generator=gen)[:k]
+    vals = torch.tensor(values, dtype=x.dtype)
+    flat[idx] = vals[torch.arange(k) % len(values)]
+    return x
+
+
+# (513, 10240) exceeds 2048 blocks x 2048 elements: the grid-stride loop
+# wraps.  F = 2056 puts a second, partial column block into the db kernel.
+@pytest.mark.parametrize("N,F", [(1, 8), (3, 1000), (70, 2056),
+                                 (513, 10240)])
+def test_bias_gelu_shapes_and_values(ext, N, F):
+    g = _gen(120)
+    x = _sprinkle(torch.randn(N, F, generator=g), _GELU_SPECIALS, g)
+    x = x.to(BF16).cuda()
+    bias = _randn_bf16(g, F)
+    dy = _randn_bf16(g, N, F)
+    y = ext.bias_gelu_fwd(x, bias)
+    y64 = ref.bias_gelu_fwd(x.double(), bias.double())
+    assert torch.isfinite(y).all()
+    torch.testing.assert_close(y.double(), y64, rtol=2e-2, atol=2e-2)
+
+    dx, db = ext.bias_gelu_bwd(dy, x, bias)
+    dx64, _ = ref.bias_gelu_bwd(dy.double(), x.double(), bias.double())
+    assert torch.isfinite(dx).all()
+    torch.testing.assert_close(dx.double(), dx64, rtol=2e-2, atol=2e-2)
+    # db is checked against the sum of the fp64 dx, but the kernel sums
+    # its own bf16-rounded dx.  The extra term is that output-rounding
+    # allowance: each summand is off by up to 2^-9 |dx|, N of them adding
+    # like a random walk, taken at 2^-8 * sqrt(N) * max|dx| per column.
+    rounding = 2.0 ** -8 * math.sqrt(N) * dx64.abs().amax(0)
+    _assert_colsum(db, dx64, "db", extra=rounding)
+
+
+# ----------------------------------------------------------------- column sum
+
+# F = 10 is what the ViT head sends through linear_bias
+@pytest.mark.parametrize("N,F", [(1, 8), (3, 10), (70, 100), (513, 2056)])
+def test_colsum_shapes(ext, N, F):
+    g = _gen(130)
+    t = (torch.randn(N, F, generator=g) * 2).to(BF16).cuda()
+    _assert_colsum(ext.colsum_bf16(t), t.double(), "colsum")
+
+
+# -------------------------------------------------------------- cross-entropy
+
+@pytest.mark.parametrize("V", [8, 1000, 2056, 51200])
+def test_cross_entropy_rows(ext, V):
+    g = _gen(140)
+    NEG = float("-inf")
+    last = V - 1
+    logits = torch.randn(6, V, generator=g)
+    tgt = [0] * 6
+    tgt[0] = 0                               # plain normals
+    logits[1] = 2.5                          # all logits equal
+    tgt[1] = min(7, last)
+    big2 = min(2047, last)                   # one +3e4, rest -3e4: target on it
+    logits[2] = -3e4
+    logits[2, big2] = 3e4
+    tgt[2] = big2
+    big3 = min(2048, last)                   # same, target off it
+    logits[3] = -3e4
+    logits[3, big3] = 3e4
+    tgt[3] = 8 if (8 < V and big3 != 8) else 0
+    # -inf (masked vocab) at both ends, 8 entries each; at V = 8 that would
+    # leave nothing finite, so 2 each there
+    k = 8 if V >= 24 else 2
+    logits[4, :k] = NEG
+    logits[4, V - k:] = NEG
+    # the largest of the target set {0, 7, 8, 2047, 2048, V-1} that is not
+    # masked; at V = 8 the set is only the two (masked) ends, so V - 3
+    tgt[4] = max([t for t in (8, 2047, 2048) if k <= t < V - k],
+                 default=V - 3)
+    logits[5] *= 50.0
+    tgt[5] = last
+    logits = logits.to(BF16).cuda()
+    targets = torch.tensor(tgt, dtype=torch.int64).cuda()
+    assert logits[4, tgt[4]].item() != NEG and logits[3, tgt[3]] < 0
+
+    loss, lse = ext.cross_entropy_fwd(logits, targets)
+    loss64, lse64 = ref.softmax_cross_entropy_fwd(logits.double(), targets)
+    print("lse got", lse.tolist(), "want", lse64.tolist())
+    # bf16 inputs are exact, so only the fp32 exp/log error (~1e-7
+    # relative) and the fp32 rounding of the result remain.  The existing
+    # 1e-3 is kept as atol; rtol carries the rows with |lse| ~ 3e4 and is
+    # 1e-5, not 1e-3, which would forgive an error of 30 there.
+    torch.testing.assert_close(lse.double(), lse64, rtol=1e-5, atol=1e-3)
+    torch.testing.assert_close(loss.double(), loss64, rtol=1e-5, atol=1e-3)
+
+    dloss = torch.randn(6, generator=g).cuda()
+    lse32 = lse64.float()
+    dlogits = ext.cross_entropy_bwd(dloss, logits, targets, lse32)
+    dl64 = ref.softmax_cross_entropy_bwd(dloss.double(), logits.double(),
+                                         targets, lse32.double())
+    assert torch.isfinite(dlogits).all()
+    torch.testing.assert_close(dlogits.double(), dl64, rtol=2e-2, atol=2e-2)
+    # softmax - onehot sums to zero; what is left is bf16 output rounding
+    rowsum = dlogits.double().sum(-1).abs()
+    bound = 2.0 ** -8 * dloss.double().abs() * math.sqrt(V)
+    assert (rowsum <= bound).all(), (rowsum.tolist(), bound.tolist())
+    masked = logits[4] == NEG
+    assert masked.sum().item() == 2 * k
+    assert (dlogits[4][masked] == 0).all()
+
+
+# ---------------------------------------------------------------------- AdamW
+
+ADAM_BF16_NUMELS = [1, 7, 8, 9, 16383, 16384, 16385, 2 * 16384 + 13]
+ADAM_FP32_NUMELS = [5, 16385]
+ADAM_GUARD = 64          # sentinel elements on each side of every tensor
+ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS = 1e-2, 0.9, 0.95, 1e-8
+ADAM_STEPS = (1, 2, 1000)
+
+# Largest relative deviation between ref.adamw_step run in fp32 and in fp64
+# on exactly the inputs of adam_inputs() below, over ADAM_STEPS and the four
+# (weight_decay, grad_scale) cases, measured on the CPU:
+#   m: 1.19e-07   v: 1.68e-07   fp32 params: 4.08e-07
+# m and v are relative to the fp64 value.  A parameter is the difference of
+# p * (1 - lr * wd) and an update of size ~lr; where the two nearly cancel,
+# the error relative to the result is unbounded for every fp32 evaluation
+# (2.6e-3 for the fp32 reference on these inputs), which would set a
+# tolerance that forgives a missing weight decay.  So for parameters the
+# deviation is taken relative to |p| + lr, the size of the terms.
+# The kernel is allowed 8x these: the margin is for another, equally valid
+# fp32 evaluation order and for powf vs Python ** in the bias correction.
+ADAM_D_M, ADAM_D_V, ADAM_D_P = 1.19e-07, 1.68e-07, 4.08e-07
+
+
+# Views that are NOT 16-byte aligned, as (dtype, numel, element offsets of
+# p, g, m, v past an aligned base).  The kernel must take its element-wise
+# path for these and never a 16-byte access.
+ADAM_MISALIGNED = [
+    # ZeRO-2 shard layout: p and g are flat[rank * shard_n:] with shard_n
+    # odd, the moments fresh allocations; short, one chunk + tail, > 2 chunks
+    (BF16, 5, (3, 3, 0, 0)),
+    (BF16, 16385, (3, 3, 0, 0)),
+    (BF16, 2 * 16384 + 13, (7, 7, 0, 0)),
+    (torch.float32, 3, (1, 1, 0, 0)),
+    (torch.float32, 16384 + 9, (1, 1, 0, 0)),
+    # all four streams at one common phase (8 B for p/g, 16 B for m/v)
+    (BF16, 16384 + 9, (4, 4, 4, 4)),
+    (torch.float32, 16385, (2, 2, 2, 2)),
+    # bucket grad view after an odd-sized param: only g is off
+    (BF16, 9, (0, 5, 0, 0)),
+    # only the moments are off
+    (BF16, 16384, (0, 0, 1, 3)),
+]
+
+
+def adam_inputs():
+    """CPU (dtype, p, g, offsets) per tensor, seeded: shared with the CPU
+    measurement of the fp32-vs-fp64 deviation above."""
+    g = _gen(150)
+    specs = [(BF16, n, (0, 0, 0, 0)) for n in ADAM_BF16_NUMELS] + \
+        [(torch.float32, n, (0, 0, 0, 0)) for n in ADAM_FP32_NUMELS] + \
+        ADAM_MISALIGNED
+    return [(dt, torch.randn(n, generator=g).to(dt),
+             torch.randn(n, generator=g).to(dt), offs)
+            for dt, n, offs in specs]
+
+
+def _guarded(t, fill, shift):
+    """A GPU buffer [guard | shift | t | guard], all but t filled with the
+    sentinel; returns (buffer, view of t).  The guard is 64 elements (128 B
+    for bf16, 256 B for fp32), so the view is 16-byte aligned exactly when
+    shift is 0 or a whole number of 16-byte groups."""
+    n = t.numel()
+    lo = ADAM_GUARD + shift
+    buf = torch.full((lo + n + ADAM_GUARD,), fill, dtype=t.dtype,
+                     device="cuda")
+    buf[lo:lo + n] = t.cuda()
+    view = buf[lo:lo + n]
+    assert (view.data_ptr() % 16 == 0) == \
+        (shift * t.element_size() % 16 == 0)
+    return buf, view, lo
+
+
+def _guards_intact(buf, lo, fill):
+    want = torch.full((buf.numel(),), fill, dtype=buf.dtype, device="cuda")
+    bits = torch.int16 if buf.dtype == BF16 else torch.int32
+    return (torch.equal(buf[:lo].view(bits), want[:lo].view(bits)) and
+            torch.equal(buf[-ADAM_GUARD:].view(bits),
+                        want[-ADAM_GUARD:].view(bits)))
+
+
+@pytest.mark.parametrize("grad_scale", [1.0, 0.5])
+@pytest.mark.parametrize("weight_decay", [0.0, 0.1])
+def test_adamw_mixed_list(ext, weight_decay, grad_scale):
+    from alpa_amd import ops
+    FILL = 1234.5
+    bufs, ps, gs, ms, vs = [], [], [], [], []
+    p64, g64, m64, v64 = [], [], [], []
+    for dt, p, g, offs in adam_inputs():
+        for src, views, shift in ((p, ps, offs[0]), (g, gs, offs[1]),
+                                  (torch.zeros(p.numel()), ms, offs[2]),
+                                  (torch.zeros(p.numel()), vs, offs[3])):
+            buf, view, lo = _guarded(src, FILL, shift)
+            bufs.append((buf, lo))
+            views.append(view)
+        p64.append(p.double())
+        g64.append(g.double())
+        m64.append(torch.zeros(p.numel(), dtype=torch.float64))
+        v64.append(torch.zeros(p.numel(), dtype=torch.float64))
+
+    worst = {"m": 0.0, "v": 0.0, "p32": 0.0}
+    for step in ADAM_STEPS:
+        ops.fused_adamw(ps, gs, ms, vs, step, lr=ADAM_LR, beta1=ADAM_B1,
+                        beta2=ADAM_B2, eps=ADAM_EPS,
+                        weight_decay=weight_decay, grad_scale=grad_scale)
+        ref.adamw_step(p64, g64, m64, v64, step, lr=ADAM_LR, beta1=ADAM_B1,
+                       beta2=ADAM_B2, eps=ADAM_EPS,
+                       weight_decay=weight_decay, grad_scale=grad_scale)
+        for i, p in enumerate(ps):
+            got_m, got_v = ms[i].double().cpu(), vs[i].double().cpu()
+            got_p = p.double().cpu()
+            worst["m"] = max(worst["m"], ((got_m - m64[i]).abs() /
+                                          m64[i].abs()).max().item())
+            worst["v"] = max(worst["v"], ((got_v - v64[i]).abs() /
+                                          v64[i].abs()).max().item())
+            # ADAM_D_M = 1.19e-07 measured -> rtol 9.5e-07
+            torch.testing.assert_close(got_m, m64[i], rtol=8 * ADAM_D_M,
+                                       atol=0)
+            # ADAM_D_V = 1.68e-07 measured -> rtol 1.3e-06
+            torch.testing.assert_close(got_v, v64[i], rtol=8 * ADAM_D_V,
+                                       atol=0)
+            if p.dtype == BF16:
+                # the kernel rounds the parameter to bf16 every step
+                torch.testing.assert_close(got_p, p64[i], rtol=2e-2,
+                                           atol=2e-2)
+            else:
+                worst["p32"] = max(worst["p32"],
+                                   ((got_p - p64[i]).abs() /
+                                    (p64[i].abs() + ADAM_LR)).max().item())
+                # ADAM_D_P = 4.08e-07 measured -> 3.3e-06 * (|p| + lr)
+                torch.testing.assert_close(got_p, p64[i], rtol=8 * ADAM_D_P,
+                                           atol=8 * ADAM_D_P * ADAM_LR)
+    print("adamw worst relative deviation", worst)
+    for buf, lo in bufs:
+        assert _guards_intact(buf, lo, FILL), "write outside a tensor"
+
+
+# -------------------------------------------------------------- fp8 quantiser
+
+def _fp8_meta(e5m2):
+    return ((57344.0, torch.float8_e5m2, 1e-3) if e5m2 else
+            (448.0, torch.float8_e4m3fn, 0.02))
+
+
+def _fp8_ref(x, scale, e5m2):
+    """q the way the kernel evaluates it: one fp32 multiply by the fp32
+    reciprocal of max(scale, 1e-12), clamp, round to nearest even."""
+    lim, dt, _ = _fp8_meta(e5m2)
+    inv = 1.0 / scale.clamp_min(1e-12)
+    return (x.float() * inv).clamp(-lim, lim).to(dt)
+
+
+def fp8_values(shape, seed):
+    """CPU bf16: randn*3 with exact zeros, -64 as the (negative) largest
+    magnitude and +-60/-64, which leave the clamp range at both test
+    scales."""
+    g = _gen(seed)
+    x = torch.randn(*shape, generator=g) * 3
+    _sprinkle(x, [0.0, -0.0, 60.0, -60.0], g)
+    x.view(-1)[1 % x.numel()] = -64.0
+    x.view(-1)[0] = 0.0
+    return x.to(BF16)
+
+
+def _fp8_input(shape, seed):
+    return fp8_values(shape, seed).cuda()
+
+
+def _fp8_order(q):
+    """fp8 bytes as integers ordered like the values (sign-magnitude)."""
+    b = q.view(torch.uint8).to(torch.int32)
+    mag = b & 0x7f
+    return torch.where((b & 0x80) != 0, -mag, mag)
+
+
+def _check_fp8(q, x, scale, amax, e5m2, name):
+    lim, _, _ = _fp8_meta(e5m2)
+    want = _fp8_ref(x, scale, e5m2)
+    assert torch.isfinite(q.float()).all()
+    # a maximum over bf16 values is exact
+    assert amax.item() == x.float().abs().amax().item()
+    ulps = (_fp8_order(q) - _fp8_order(want)).abs()
+    assert ulps.max().item() <= 1, f"{name}: off by {ulps.max().item()} ulp"
+    # tests/test_fp8_gpu.py lets 0.1% (e4m3) / 1% (e5m2) of the elements
+    # differ from its divide-form reference.  Against the multiply form the
+    # kernel uses, the observed share is 0 in every case here (and so is
+    # the share between the two reference forms on these inputs), so the
+    # cap is 0.
+    share = (ulps != 0).float().mean().item()
+    print(f"{name}: share differing = {share:.3g}")
+    assert share == 0.0, (name, share)
+    over = x.float().abs() / scale > lim
+    assert over.any()
+    assert torch.equal(q.float()[over], torch.sign(x.float()[over]) * lim)
+
+
+@pytest.mark.parametrize("e5m2", [False, True])
+@pytest.mark.parametrize("numel", [8, 4096 * 2048 + 24])
+def test_fp8_quantize_single_layout(ext, numel, e5m2):
+    """dual=False; the larger size is past 4096 blocks x 2048 elements, so
+    the grid-stride loop wraps."""
+    x = _fp8_input((numel,), 160)
+    scale = torch.tensor([_fp8_meta(e5m2)[2]], device="cuda")
+    q, qt, amax = ext.fp8_quantize(x, scale, False, e5m2)
+    assert q.shape == x.shape
+    _check_fp8(q, x, scale, amax, e5m2, f"single[{numel}]")
+
+
+@pytest.mark.parametrize("e5m2", [False, True])
+@pytest.mark.parametrize("M,N", [(1, 8), (64, 64), (65, 201), (130, 63)])
+def test_fp8_quantize_dual_layout(ext, M, N, e5m2):
+    x = _fp8_input((M, N), 161)
+    scale = torch.tensor([_fp8_meta(e5m2)[2]], device="cuda")
+    q, qt, amax = ext.fp8_quantize(x, scale, True, e5m2)
+    assert torch.equal(qt.view(torch.uint8), q.view(torch.uint8).t())
+    _check_fp8(q, x, scale, amax, e5m2, f"dual[{M}x{N}]")
+
+
+@pytest.mark.parametrize("e5m2", [False, True])
+@pytest.mark.parametrize("dual", [False, True])
+def test_fp8_quantize_all_zero(ext, dual, e5m2):
+    x = torch.zeros(65, 200, dtype=BF16, device="cuda")
+    scale = torch.tensor([_fp8_meta(e5m2)[2]], device="cuda")
+    q, qt, amax = ext.fp8_quantize(x, scale, dual, e5m2)
+    assert amax.item() == 0.0
+    assert (q.view(torch.uint8) & 0x7f).max().item() == 0
+    if dual:
+        assert (qt.view(torch.uint8) & 0x7f).max().item() == 0
+
+
+# ------------------------------------------------------------ argument checks
+# GPU tensors, but every call must be refused before a kernel is launched.
+
+def _z(*shape, dtype=BF16):
+    return torch.zeros(*shape, dtype=dtype, device="cuda")
+
+
+def test_add_layer_norm_rejects_h_not_multiple_of_8(ext):
+    with pytest.raises(RuntimeError):
+        ext.add_layer_norm_fwd(_z(4, 12), _z(4, 12), _z(12), _z(12), EPS)
+    with pytest.raises(RuntimeError):
+        ext.add_layer_norm_fwd(_z(4, 12), None, _z(12), _z(12), EPS)
+
+
+@pytest.mark.parametrize("bad", ["fp32", "short", "long", "strided"])
+@pytest.mark.parametrize("which", ["w", "b"])
+def test_layer_norm_fwd_rejects_bad_vectors(ext, which, bad):
+    H = 64
+    vec = {"fp32": _z(H, dtype=torch.float32), "short": _z(H - 8),
+           "long": _z(H + 8), "strided": _z(2 * H)[::2]}[bad]
+    w, b = (vec, _z(H)) if which == "w" else (_z(H), vec)
+    with pytest.raises(RuntimeError):
+        ext.layer_norm_fwd(_z(4, H), w, b, EPS)
+    with pytest.raises(RuntimeError):
+        ext.add_layer_norm_fwd(_z(4, H), _z(4, H), w, b, EPS)
+    with pytest.raises(RuntimeError):
+        ext.add_layer_norm_fwd(_z(4, H), None, w, b, EPS)
+
+
+@pytest.mark.parametrize("bad", ["fp32", "short", "long", "strided"])
+def test_bias_gelu_rejects_bad_bias(ext, bad):
+    F = 64
+    bias = {"fp32": _z(F, dtype=torch.float32), "short": _z(F - 8),
+            "long": _z(F + 8), "strided": _z(2 * F)[::2]}[bad]
+    with pytest.raises(RuntimeError):
+        ext.bias_gelu_fwd(_z(4, F), bias)
+    with pytest.raises(RuntimeError):
+        ext.bias_gelu_bwd(_z(4, F), _z(4, F), bias)
+
+
+def test_backward_entries_reject_mismatched_shapes(ext):
+    N, H = 4, 64
+    x, w = _z(N, H), _z(H)
+    st = _z(N, dtype=torch.float32)
+    for dy in (_z(N - 1, H), _z(N, H + 8), _z(N + 1, H)):
+        with pytest.raises(RuntimeError):
+            ext.layer_norm_bwd(dy, x, w, st, st)
+        with pytest.raises(RuntimeError):
+            ext.add_layer_norm_bwd(dy, None, x, w, st, st)
+        with pytest.raises(RuntimeError):
+            ext.bias_gelu_bwd(dy, x, w)
+    # x (h) of another shape than dy
+    for xx in (_z(N + 1, H), _z(N, H - 8)):
+        with pytest.raises(RuntimeError):
+            ext.layer_norm_bwd(_z(N, H), xx, w, st, st)
+        with pytest.raises(RuntimeError):
+            ext.add_layer_norm_bwd(_z(N, H), None, xx, w, st, st)
+        with pytest.raises(RuntimeError):
+            ext.bias_gelu_bwd(_z(N, H), xx, w)
+    with pytest.raises(RuntimeError):     # residual grad of another shape
+        ext.add_layer_norm_bwd(_z(N, H), _z(N - 1, H), x, w, st, st)
+    # statistics: fp32 [N]
+    for bad in (_z(N - 1, dtype=torch.float32), _z(N, dtype=BF16),
+                _z(N, dtype=torch.float64)):
+        with pytest.raises(RuntimeError):
+            ext.layer_norm_bwd(_z(N, H), x, w, bad, st)
+        with pytest.raises(RuntimeError):
+            ext.layer_norm_bwd(_z(N, H), x, w, st, bad)
+        with pytest.raises(RuntimeError):
+            ext.add_layer_norm_bwd(_z(N, H), None, x, w, st, bad)

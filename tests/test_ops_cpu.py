@@ -133,3 +133,79 @@ def test_rms_norm_reference():
     dx, dw = ref.rms_norm_bwd(dy, x.detach(), w.detach(), rstd)
     torch.testing.assert_close(dx, x.grad, rtol=1e-5, atol=1e-5)
     torch.testing.assert_close(dw, w.grad, rtol=1e-5, atol=1e-5)
+
+
+# ------------------- multi-tensor AdamW descriptor tables -------------------
+
+def _adam_tables_fresh(params, grads, ms, vs):
+    from alpa_amd import ops
+    return ops._adam_tables(params, grads, ms, vs)
+
+
+@pytest.fixture
+def clear_adam_cache():
+    from alpa_amd import ops
+    ops._ADAM_TABLE_CACHE.clear()
+    yield
+    ops._ADAM_TABLE_CACHE.clear()
+
+
+def test_adam_tables_follow_new_moment_buffers(clear_adam_cache):
+    """A second optimizer over the same params/grads brings fresh moment
+    tensors: the descriptor rows must point at them, not at the first
+    optimizer's (cached) buffers."""
+    p, g = [torch.zeros(100)], [torch.zeros(100)]
+    m1, v1 = [torch.zeros(100)], [torch.zeros(100)]
+    m2, v2 = [torch.zeros(100)], [torch.zeros(100)]
+    d1, _ = _adam_tables_fresh(p, g, m1, v1)
+    d2, _ = _adam_tables_fresh(p, g, m2, v2)
+    assert d1[0, 2].item() == m1[0].data_ptr()
+    assert d1[0, 3].item() == v1[0].data_ptr()
+    assert d2[0, 0].item() == p[0].data_ptr()
+    assert d2[0, 1].item() == g[0].data_ptr()
+    assert d2[0, 2].item() == m2[0].data_ptr()
+    assert d2[0, 3].item() == v2[0].data_ptr()
+    # and an unchanged call still hits the cache
+    assert _adam_tables_fresh(p, g, m2, v2)[0] is d2
+
+
+def test_adam_tables_same_pointers_other_size_or_dtype(clear_adam_cache):
+    """Same base pointers, different numel or dtype (what the caching
+    allocator produces when a block is reused): descriptors and chunk
+    tables must describe the tensors passed in."""
+    pbuf = torch.zeros(2 * 16384 + 64)
+    gbuf = torch.zeros(2 * 16384 + 64)
+    m, v = torch.zeros(2 * 16384 + 64), torch.zeros(2 * 16384 + 64)
+    n_small, n_big = 1000, 16384 + 5
+    d, c = _adam_tables_fresh([pbuf[:n_small]], [gbuf[:n_small]],
+                              [m[:n_small]], [v[:n_small]])
+    assert d[0, 4].item() == n_small and d[0, 5].item() == 0
+    assert c.shape == (1, 2)
+    d, c = _adam_tables_fresh([pbuf[:n_big]], [gbuf[:n_big]], [m[:n_big]],
+                              [v[:n_big]])
+    assert d[0, 4].item() == n_big and d[0, 5].item() == 0
+    assert c.tolist() == [[0, 0], [0, 1]]
+    # same bytes viewed as bf16: numel doubles, the dtype flag flips
+    pb = pbuf[:n_small].view(torch.bfloat16)
+    gb = gbuf[:n_small].view(torch.bfloat16)
+    assert pb.data_ptr() == pbuf.data_ptr()
+    d, c = _adam_tables_fresh([pb], [gb], [m[:2 * n_small]],
+                              [v[:2 * n_small]])
+    assert d[0, 4].item() == 2 * n_small and d[0, 5].item() == 1
+    # same numel, other dtype, same pointers
+    pbuf16 = pbuf.view(torch.bfloat16)
+    gbuf16 = gbuf.view(torch.bfloat16)
+    d, _ = _adam_tables_fresh([pbuf16[:n_small]], [gbuf16[:n_small]],
+                              [m[:n_small]], [v[:n_small]])
+    assert d[0, 4].item() == n_small and d[0, 5].item() == 1
+
+
+@pytest.mark.parametrize("numel,rows", [(16384, 1), (16385, 2)])
+def test_adam_tables_chunk_rows(clear_adam_cache, numel, rows):
+    """One chunk-table row per started ADAM_CHUNK (16384) elements."""
+    t = [torch.zeros(numel, dtype=torch.bfloat16)]
+    s = [torch.zeros(numel)]
+    d, c = _adam_tables_fresh(t, [torch.zeros_like(t[0])], s,
+                              [torch.zeros(numel)])
+    assert d[0, 4].item() == numel and d[0, 5].item() == 1
+    assert c.tolist() == [[0, i] for i in range(rows)]
