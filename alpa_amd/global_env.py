@@ -59,6 +59,13 @@ class GlobalConfig:
     fp8_dx_bf16: bool = field(
         default_factory=lambda: os.environ.get("ALPA_AMD_FP8_DX_BF16",
                                                "0") == "1")
+    #: route MoE tokens through the fused HIP kernels (top-2 gate, capacity
+    #: slots, dispatch, combine; ops/csrc/moe_route.hip) when the input is
+    #: inside their envelope (ops.moe_fused_ok).  They never read the
+    #: device back, unlike the torch-op path with its data-dependent
+    #: shapes.  ALPA_AMD_MOE_FUSED=0 keeps the torch-op path everywhere
+    moe_fused_routing: bool = field(
+        default_factory=lambda: _env_bool("ALPA_AMD_MOE_FUSED", True))
     #: scatter-allgather resharding rewrite at replicated stage
     #: boundaries (ship 1/R per replica + intra-group all-gather;
     #: reference use_local_allgather, global_env.py:72)

@@ -5,7 +5,9 @@ built from ``csrc/``); CPU tensors -> the pure-torch reference
 (`reference.py`).  Plain unfused GEMMs go through ``torch.matmul``
 (hipBLASLt on ROCm) — hand-written kernels cover the *fused* ops where
 library calls can't: LayerNorm, flash attention, bias+GeLU epilogue,
-softmax-cross-entropy over the 51200-wide vocab, and multi-tensor AdamW.
+softmax-cross-entropy over the 51200-wide vocab, multi-tensor AdamW, and
+the sync-free top-2 MoE routing path: moe_top2_route (gate + capacity
+slots), moe_dispatch and moe_combine.
 
 Kernel-level contract mirrors the reference's compiled-HLO op inventory
 (GEMM+epilogue, attention, LayerNorm, fused Adam,
@@ -14,7 +16,7 @@ grad accumulation, collectives).
 from __future__ import annotations
 
 import math
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
@@ -24,7 +26,8 @@ from ._backend import hip_ops, hip_ops_available, use_hip
 __all__ = [
     "layer_norm", "add_layer_norm", "bias_gelu", "flash_attention",
     "flash_attention_qkv", "softmax_cross_entropy", "fused_adamw",
-    "hip_ops_available",
+    "hip_ops_available", "MoERouting", "moe_top2_route", "moe_dispatch",
+    "moe_combine", "moe_fused_ok",
 ]
 
 
@@ -451,6 +454,140 @@ def fused_adamw(params: List[torch.Tensor], grads: List[torch.Tensor],
     else:
         ref.adamw_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1,
                        beta2, eps, weight_decay, grad_scale)
+
+
+# ------------------------------- MoE routing -------------------------------
+
+
+class MoERouting(NamedTuple):
+    """Result of :func:`moe_top2_route` for N tokens, E experts, capacity C.
+
+    w1, w2 [N] gate weights (normalised before capacity drops); idx1, idx2
+    [N] chosen experts; slot1, slot2 [N] slot in the [E*C] dispatch buffer
+    or -1 when dropped; src [E*C] token in each slot or -1; aux_loss the
+    GShard load-balance loss.  Integer fields are int32 and carry no
+    gradient."""
+    w1: torch.Tensor
+    w2: torch.Tensor
+    idx1: torch.Tensor
+    idx2: torch.Tensor
+    slot1: torch.Tensor
+    slot2: torch.Tensor
+    src: torch.Tensor
+    aux_loss: torch.Tensor
+
+
+class _MoeTop2Route(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, logits, capacity):
+        logits = logits.contiguous()
+        if use_hip(logits):
+            outs = hip_ops().moe_route_fwd(logits, capacity)
+        else:
+            outs = ref.moe_top2_route(logits, capacity)
+        w1, w2, idx1, idx2, slot1, slot2, src, aux, count1 = outs
+        ctx.save_for_backward(logits, idx1, idx2, w1, w2, count1)
+        ctx.mark_non_differentiable(idx1, idx2, slot1, slot2, src)
+        return w1, w2, idx1, idx2, slot1, slot2, src, aux
+
+    @staticmethod
+    def backward(ctx, dw1, dw2, _i1, _i2, _s1, _s2, _src, daux):
+        logits, idx1, idx2, w1, w2, count1 = ctx.saved_tensors
+        if use_hip(logits):
+            return hip_ops().moe_route_bwd(
+                logits, idx1, idx2, w1, w2, count1, dw1.float().contiguous(),
+                dw2.float().contiguous(), daux.float().contiguous()), None
+        return ref.moe_top2_route_bwd(logits, idx1, idx2, w1, w2, count1,
+                                      dw1, dw2, daux), None
+
+
+def moe_top2_route(logits: torch.Tensor, capacity: int) -> MoERouting:
+    """Top-2 gate + capacity slot assignment over logits [N, E].
+
+    Token order decides who keeps a slot, the lowest expert index wins a
+    tie, and every output shape depends on (N, E, capacity) only — the op
+    never reads the device back, so it can sit inside a captured graph.
+    Gradients flow to logits through w1, w2 and aux_loss."""
+    return MoERouting(*_MoeTop2Route.apply(logits, int(capacity)))
+
+
+class _MoeDispatch(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, x, src, slot1, slot2):
+        x = x.contiguous()
+        ctx.save_for_backward(slot1, slot2)
+        if use_hip(x):
+            return hip_ops().moe_dispatch(x, src)
+        return ref.moe_dispatch(x, src)
+
+    @staticmethod
+    def backward(ctx, g):
+        slot1, slot2 = ctx.saved_tensors
+        if use_hip(g):
+            dx = hip_ops().moe_combine(g.contiguous(), None, None, slot1,
+                                       slot2)
+        else:
+            dx = ref.moe_dispatch_bwd(g, slot1, slot2)
+        return dx, None, None, None
+
+
+def moe_dispatch(x: torch.Tensor, routing: MoERouting) -> torch.Tensor:
+    """x [N, H] -> [E*C, H]: slot s holds x[routing.src[s]], empty slots
+    are zero.  One gather pass; backward is a gather too."""
+    return _MoeDispatch.apply(x, routing.src, routing.slot1, routing.slot2)
+
+
+class _MoeCombine(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, y, w1, w2, slot1, slot2, src):
+        y = y.contiguous()
+        ctx.save_for_backward(y, w1, w2, slot1, slot2, src)
+        if use_hip(y):
+            return hip_ops().moe_combine(y, w1.float().contiguous(),
+                                         w2.float().contiguous(), slot1,
+                                         slot2)
+        return ref.moe_combine(y, w1, w2, slot1, slot2)
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, w1, w2, slot1, slot2, src = ctx.saved_tensors
+        if use_hip(y):
+            dout = dout.contiguous()
+            dy = hip_ops().moe_dispatch(dout, src, slot1,
+                                        w1.float().contiguous(),
+                                        w2.float().contiguous())
+            dw1, dw2 = hip_ops().moe_combine_dw(dout, y, slot1, slot2)
+            dw1, dw2 = dw1.to(w1.dtype), dw2.to(w2.dtype)
+        else:
+            dy, dw1, dw2 = ref.moe_combine_bwd(dout, y, w1, w2, slot1,
+                                               slot2, src)
+        return dy, dw1, dw2, None, None, None
+
+
+def moe_combine(y: torch.Tensor, routing: MoERouting) -> torch.Tensor:
+    """y [E*C, H] -> [N, H]: out[t] = w1*y[slot1[t]] + w2*y[slot2[t]] with
+    dropped choices skipped; fp32 sum, rounded once.  Gradients flow to y
+    and to the gate weights."""
+    return _MoeCombine.apply(y, routing.w1, routing.w2, routing.slot1,
+                             routing.slot2, routing.src)
+
+
+def moe_fused_ok(x: torch.Tensor, num_experts: int,
+                 capacity: Optional[int] = None) -> bool:
+    """Envelope of the HIP routing kernels (csrc/moe_route.hip; the
+    bindings check the same): bf16 on the GPU, H % 8 == 0 for the 16-byte
+    row accesses, 2 <= E <= 128, E * capacity < 2^31."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16):
+        return False
+    if x.shape[-1] < 8 or x.shape[-1] % 8 != 0 or \
+            not 2 <= num_experts <= 128:
+        return False
+    if capacity is not None and num_experts * capacity >= 2 ** 31:
+        return False
+    return use_hip(x)
 
 
 # ----------------------------- skinny decode GEMM --------------------------

@@ -537,6 +537,184 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
   return {dq, dk, dv};
 }
 
+// ------------------------------ MoE routing ------------------------------
+
+void check_i32_vec(const at::Tensor& t, const char* name, int64_t n) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32");
+  TORCH_CHECK(t.is_contiguous() && t.numel() == n, name,
+              " must be contiguous with ", n, " elements");
+}
+
+// bf16 [rows, H] read or written with 16-byte accesses
+void check_moe_rows(const at::Tensor& t, const char* name) {
+  check_bf16_contig(t, name);
+  TORCH_CHECK(t.dim() == 2, name, " must be 2-D");
+  TORCH_CHECK(t.size(1) % 8 == 0 && t.size(1) >= 8, name,
+              ": H must be a positive multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.const_data_ptr()) % 16 == 0,
+              name, " must be 16-byte aligned");
+}
+
+constexpr int64_t kMoeMaxTokens = int64_t(1) << 30;
+
+// logits [N, E] bf16 -> (w1, w2, idx1, idx2, slot1, slot2, src, aux,
+// count1); every shape depends on (N, E, C) only and nothing is read back
+std::vector<at::Tensor> moe_route_fwd(const at::Tensor& logits,
+                                      int64_t capacity) {
+  check_bf16_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits must be [N, E]");
+  const int64_t N = logits.size(0), E = logits.size(1), C = capacity;
+  TORCH_CHECK(E >= 2 && E <= 128, "num_experts must be in [2, 128], got ", E);
+  TORCH_CHECK(C >= 1, "capacity must be >= 1");
+  TORCH_CHECK(C < (int64_t(1) << 31) / E, "E * capacity must be < 2^31");
+  TORCH_CHECK(N <= kMoeMaxTokens, "at most 2^30 tokens");
+  auto f32 = logits.options().dtype(at::kFloat);
+  auto i32 = logits.options().dtype(at::kInt);
+  auto w1 = at::empty({N}, f32), w2 = at::empty({N}, f32);
+  auto idx1 = at::empty({N}, i32), idx2 = at::empty({N}, i32);
+  auto slot1 = at::empty({N}, i32), slot2 = at::empty({N}, i32);
+  if (N == 0) {
+    return {w1, w2, idx1, idx2, slot1, slot2, at::full({E * C}, -1, i32),
+            at::zeros({}, f32), at::zeros({E}, i32)};
+  }
+  auto src = at::empty({E * C}, i32);
+  auto aux = at::empty({}, f32);
+  auto count1 = at::empty({E}, i32);
+  const int64_t nblocks = (N + 255) / 256;
+  auto hist = at::empty({2, nblocks, E}, i32);
+  auto ppart = at::empty({nblocks, E}, f32);
+  auto psum = at::empty({E}, f32);
+  int* hist1 = (int*)hist.mutable_data_ptr();
+  int* hist2 = hist1 + nblocks * E;
+  HIP_OK(launch_moe_route(
+      logits.const_data_ptr(), (float*)w1.mutable_data_ptr(),
+      (float*)w2.mutable_data_ptr(), (int*)idx1.mutable_data_ptr(),
+      (int*)idx2.mutable_data_ptr(), (int*)slot1.mutable_data_ptr(),
+      (int*)slot2.mutable_data_ptr(), hist1, hist2,
+      (float*)ppart.mutable_data_ptr(), N, E, cur_stream()));
+  at::sum_out(psum, ppart, {0});
+  HIP_OK(launch_moe_slots(
+      (const int*)idx1.const_data_ptr(), (const int*)idx2.const_data_ptr(),
+      hist1, hist2, (const float*)psum.const_data_ptr(),
+      (int*)count1.mutable_data_ptr(), (float*)aux.mutable_data_ptr(),
+      (int*)slot1.mutable_data_ptr(), (int*)slot2.mutable_data_ptr(),
+      (int*)src.mutable_data_ptr(), N, E, C, cur_stream()));
+  return {w1, w2, idx1, idx2, slot1, slot2, src, aux, count1};
+}
+
+at::Tensor moe_route_bwd(const at::Tensor& logits, const at::Tensor& idx1,
+                         const at::Tensor& idx2, const at::Tensor& w1,
+                         const at::Tensor& w2, const at::Tensor& count1,
+                         const at::Tensor& dw1, const at::Tensor& dw2,
+                         const at::Tensor& daux) {
+  check_bf16_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits must be [N, E]");
+  const int64_t N = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(E >= 2 && E <= 128, "num_experts must be in [2, 128], got ", E);
+  TORCH_CHECK(N <= kMoeMaxTokens, "at most 2^30 tokens");
+  check_i32_vec(idx1, "idx1", N);
+  check_i32_vec(idx2, "idx2", N);
+  check_i32_vec(count1, "count1", E);
+  check_row_stats(w1, "w1", N);
+  check_row_stats(w2, "w2", N);
+  check_row_stats(dw1, "dw1", N);
+  check_row_stats(dw2, "dw2", N);
+  check_row_stats(daux, "daux", 1);
+  auto dlogits = at::empty_like(logits);
+  if (N == 0) return dlogits;
+  HIP_OK(launch_moe_route_bwd(
+      logits.const_data_ptr(), (const int*)idx1.const_data_ptr(),
+      (const int*)idx2.const_data_ptr(), (const float*)w1.const_data_ptr(),
+      (const float*)w2.const_data_ptr(), (const int*)count1.const_data_ptr(),
+      (const float*)dw1.const_data_ptr(), (const float*)dw2.const_data_ptr(),
+      (const float*)daux.const_data_ptr(), dlogits.mutable_data_ptr(), N, E,
+      cur_stream()));
+  return dlogits;
+}
+
+// out[s] = x[src[s]] or zeros.  With (slot1, w1, w2) row s is also scaled
+// by the gate weight of the choice that owns it (the combine's dy).
+at::Tensor moe_dispatch(const at::Tensor& x, const at::Tensor& src,
+                        const c10::optional<at::Tensor>& slot1,
+                        const c10::optional<at::Tensor>& w1,
+                        const c10::optional<at::Tensor>& w2) {
+  check_moe_rows(x, "x");
+  const int64_t N = x.size(0), H = x.size(1), S = src.numel();
+  check_i32_vec(src, "src", S);
+  TORCH_CHECK(S < (int64_t(1) << 31), "E * capacity must be < 2^31");
+  TORCH_CHECK(N <= kMoeMaxTokens, "at most 2^30 tokens");
+  const bool scaled = slot1.has_value();
+  TORCH_CHECK(w1.has_value() == scaled && w2.has_value() == scaled,
+              "slot1, w1 and w2 go together");
+  if (scaled) {
+    check_i32_vec(*slot1, "slot1", N);
+    check_row_stats(*w1, "w1", N);
+    check_row_stats(*w2, "w2", N);
+  }
+  auto out = at::empty({S, H}, x.options());
+  if (S == 0) return out;
+  HIP_OK(launch_moe_dispatch(
+      x.const_data_ptr(), (const int*)src.const_data_ptr(),
+      scaled ? (const int*)slot1->const_data_ptr() : nullptr,
+      scaled ? (const float*)w1->const_data_ptr() : nullptr,
+      scaled ? (const float*)w2->const_data_ptr() : nullptr,
+      out.mutable_data_ptr(), S, N, H, cur_stream()));
+  return out;
+}
+
+// out[t] = w1[t] * y[slot1[t]] + w2[t] * y[slot2[t]] (dropped terms
+// skipped); without weights the plain sum (the dispatch's dx)
+at::Tensor moe_combine(const at::Tensor& y,
+                       const c10::optional<at::Tensor>& w1,
+                       const c10::optional<at::Tensor>& w2,
+                       const at::Tensor& slot1, const at::Tensor& slot2) {
+  check_moe_rows(y, "y");
+  const int64_t S = y.size(0), H = y.size(1), N = slot1.numel();
+  TORCH_CHECK(S < (int64_t(1) << 31), "E * capacity must be < 2^31");
+  TORCH_CHECK(N <= kMoeMaxTokens, "at most 2^30 tokens");
+  check_i32_vec(slot1, "slot1", N);
+  check_i32_vec(slot2, "slot2", N);
+  TORCH_CHECK(w1.has_value() == w2.has_value(), "w1 and w2 go together");
+  if (w1.has_value()) {
+    check_row_stats(*w1, "w1", N);
+    check_row_stats(*w2, "w2", N);
+  }
+  auto out = at::empty({N, H}, y.options());
+  if (N == 0) return out;
+  HIP_OK(launch_moe_combine(
+      y.const_data_ptr(),
+      w1.has_value() ? (const float*)w1->const_data_ptr() : nullptr,
+      w2.has_value() ? (const float*)w2->const_data_ptr() : nullptr,
+      (const int*)slot1.const_data_ptr(), (const int*)slot2.const_data_ptr(),
+      out.mutable_data_ptr(), N, S, H, cur_stream()));
+  return out;
+}
+
+// (dw1, dw2)[t] = <dout[t], y[slot_k[t]]> in fp32, 0 when dropped
+std::vector<at::Tensor> moe_combine_dw(const at::Tensor& dout,
+                                       const at::Tensor& y,
+                                       const at::Tensor& slot1,
+                                       const at::Tensor& slot2) {
+  check_moe_rows(dout, "dout");
+  check_moe_rows(y, "y");
+  const int64_t N = dout.size(0), H = dout.size(1), S = y.size(0);
+  TORCH_CHECK(y.size(1) == H, "dout and y must share H");
+  TORCH_CHECK(S < (int64_t(1) << 31), "E * capacity must be < 2^31");
+  TORCH_CHECK(N <= kMoeMaxTokens, "at most 2^30 tokens");
+  check_i32_vec(slot1, "slot1", N);
+  check_i32_vec(slot2, "slot2", N);
+  auto f32 = dout.options().dtype(at::kFloat);
+  auto dw1 = at::empty({N}, f32), dw2 = at::empty({N}, f32);
+  if (N == 0) return {dw1, dw2};
+  HIP_OK(launch_moe_combine_dw(
+      dout.const_data_ptr(), y.const_data_ptr(),
+      (const int*)slot1.const_data_ptr(), (const int*)slot2.const_data_ptr(),
+      (float*)dw1.mutable_data_ptr(), (float*)dw2.mutable_data_ptr(), N, S,
+      H, cur_stream()));
+  return {dw1, dw2};
+}
+
 at::Tensor mfma_probe(const at::Tensor& a, const at::Tensor& b) {
   check_bf16_contig(a, "a");
   auto d = at::empty({16, 16}, a.options().dtype(at::kFloat));
@@ -592,7 +770,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // alpa_amd/version.py (reference check_alpa_jaxlib_version, version.py:10)
   // 3: the experimental attention entries (attn_fwd_v2, attn_fwd_sbuf,
   // attn_fwd_ablate, attn_bwd_dkv_ablate) were removed
-  m.attr("ABI_VERSION") = 3;
+  // 4: MoE routing entries (moe_route_fwd/bwd, moe_dispatch, moe_combine,
+  // moe_combine_dw) added
+  m.attr("ABI_VERSION") = 4;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)");
   m.def("add_layer_norm_fwd", &add_layer_norm_fwd,
@@ -630,6 +810,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("alibi") = py::none());
   m.def("attn_bwd_blocked", &attn_bwd_blocked,
         "attention bwd (blocked hipBLASLt reference)");
+  m.def("moe_route_fwd", &moe_route_fwd,
+        "top-2 gate + capacity slots, sync-free (gfx950)");
+  m.def("moe_route_bwd", &moe_route_bwd, "top-2 gate backward (gfx950)");
+  m.def("moe_dispatch", &moe_dispatch, "MoE token dispatch gather (gfx950)",
+        py::arg("x"), py::arg("src"), py::arg("slot1") = py::none(),
+        py::arg("w1") = py::none(), py::arg("w2") = py::none());
+  m.def("moe_combine", &moe_combine, "MoE weighted combine gather (gfx950)");
+  m.def("moe_combine_dw", &moe_combine_dw,
+        "MoE combine gate-weight gradient (gfx950)");
   m.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 layout probe");
   m.def("mfma_probe32", &mfma_probe32, "MFMA 32x32x16 layout probe");
 }

@@ -94,6 +94,42 @@ hipError_t launch_attn_bwd(const void* q, const void* k, const void* v,
                            int causal, const float* alibi,
                            const int64_t* strides, hipStream_t stream);
 
+// ---- moe_route.hip ----
+// top-2 + in-block ranks (left in slot1/slot2) + per-256-token-block
+// histograms and softmax column partials, all [ceil(N/256), E]
+hipError_t launch_moe_route(const void* logits, float* w1, float* w2,
+                            int* idx1, int* idx2, int* slot1, int* slot2,
+                            int* hist1, int* hist2, float* ppart, int64_t N,
+                            int64_t E, hipStream_t stream);
+// fills src with -1, scans the histograms in place, writes count1 and aux,
+// then turns the ranks in slot1/slot2 into slots and fills src
+hipError_t launch_moe_slots(const int* idx1, const int* idx2, int* hist1,
+                            int* hist2, const float* psum, int* count1,
+                            float* aux, int* slot1, int* slot2, int* src,
+                            int64_t N, int64_t E, int64_t C,
+                            hipStream_t stream);
+hipError_t launch_moe_route_bwd(const void* logits, const int* idx1,
+                                const int* idx2, const float* w1,
+                                const float* w2, const int* count1,
+                                const float* dw1, const float* dw2,
+                                const float* daux, void* dlogits, int64_t N,
+                                int64_t E, hipStream_t stream);
+// x [N, H] -> out [S, H]; slot1/w1/w2 all null or all given (scaled rows)
+hipError_t launch_moe_dispatch(const void* x, const int* src,
+                               const int* slot1_or_null,
+                               const float* w1_or_null,
+                               const float* w2_or_null, void* out, int64_t S,
+                               int64_t N, int64_t H, hipStream_t stream);
+// y [S, H] -> out [N, H]; null weights mean 1
+hipError_t launch_moe_combine(const void* y, const float* w1_or_null,
+                              const float* w2_or_null, const int* slot1,
+                              const int* slot2, void* out, int64_t N,
+                              int64_t S, int64_t H, hipStream_t stream);
+hipError_t launch_moe_combine_dw(const void* dout, const void* y,
+                                 const int* slot1, const int* slot2,
+                                 float* dw1, float* dw2, int64_t N, int64_t S,
+                                 int64_t H, hipStream_t stream);
+
 // ---- mfma_probe.hip ----
 hipError_t launch_mfma_probe(const void* a, const void* b, float* d,
                              hipStream_t stream);

@@ -209,3 +209,152 @@ def adamw_step(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float,
         denom = (v / bc2).sqrt_().add_(eps)
         pf.addcdiv_(m / bc1, denom, value=-lr)
         p.copy_(pf.to(p.dtype))
+
+
+# ------------------------------ MoE routing --------------------------------
+# Fixed-shape, sync-free top-2 routing: no boolean indexing, no nonzero.
+# Integer outputs are int32, like the HIP kernels'.
+
+def _moe_top2_indices(lf: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """idx1 = argmax, idx2 = argmax over the rest; the lowest index wins a
+    tie, stated explicitly rather than left to topk/argmax.
+
+    A NaN never wins a comparison: it counts as below everything, except
+    that a NaN in the column a scan would start from (column 0 for idx1,
+    the lowest column != idx1 for idx2) is never displaced.  This is what
+    a left-to-right scan with a strict '>' gives, and it keeps
+    0 <= idx1 != idx2 < E for any row."""
+    N, E = lf.shape
+    ar = torch.arange(E, device=lf.device).expand(N, E)
+    nan = torch.isnan(lf)
+    ninf = torch.full_like(lf, float("-inf"))
+    pinf = torch.full_like(lf, float("inf"))
+    key = torch.where(nan, ninf, lf)
+    key1 = torch.where(nan & (ar == 0), pinf, key)
+    m1 = key1.max(dim=-1, keepdim=True).values
+    idx1 = torch.where(key1 == m1, ar, E).min(dim=-1).values
+    first = ar == idx1.unsqueeze(-1)
+    j0 = (idx1 == 0).long().unsqueeze(-1)
+    key2 = torch.where(nan & (ar == j0), pinf, key)
+    m2 = torch.where(first, ninf, key2).max(dim=-1, keepdim=True).values
+    idx2 = torch.where((key2 == m2) & ~first, ar, E).min(dim=-1).values
+    return idx1, idx2
+
+
+def moe_top2_route(logits: torch.Tensor, capacity: int):
+    """Top-2 gate with capacity slots.  logits [N, E] ->
+    (w1, w2, idx1, idx2, slot1, slot2, src, aux, count1).
+
+    p = softmax(logits); w_k = p_k / (p1 + p2), normalised before drops;
+    pos1[t] counts earlier tokens with the same first choice, pos2[t]
+    starts behind min(count1, C); slot_k = idx_k * C + pos_k, or -1 when
+    pos_k >= C; src[s] is the token in slot s or -1;
+    aux = E * sum_e mean_t(p[t, e]) * count1[e] / N.  Written in
+    differentiable torch ops, so autograd through w1, w2 and aux works."""
+    lf = _up(logits)
+    N, E = lf.shape
+    C = int(capacity)
+    p = torch.softmax(lf, dim=-1)
+    idx1, idx2 = _moe_top2_indices(lf.detach())
+    p1 = p.gather(1, idx1.unsqueeze(-1)).squeeze(-1)
+    p2 = p.gather(1, idx2.unsqueeze(-1)).squeeze(-1)
+    den = p1 + p2
+    w1, w2 = p1 / den, p2 / den
+
+    ar = torch.arange(E, device=lf.device)
+    oh1 = (idx1.unsqueeze(-1) == ar).long()
+    oh2 = (idx2.unsqueeze(-1) == ar).long()
+    count1 = oh1.sum(0)
+    pos1 = ((oh1.cumsum(0) - oh1) * oh1).sum(-1)
+    pos2 = ((oh2.cumsum(0) - oh2 + count1.clamp(max=C)) * oh2).sum(-1)
+    none = torch.full_like(pos1, -1)
+    slot1 = torch.where(pos1 < C, idx1 * C + pos1, none)
+    slot2 = torch.where(pos2 < C, idx2 * C + pos2, none)
+    # dropped choices land in one spare entry past the end
+    t = torch.arange(N, device=lf.device)
+    spare = torch.full_like(pos1, E * C)
+    src = torch.full((E * C + 1,), -1, dtype=torch.long, device=lf.device)
+    src.scatter_(0, torch.where(slot1 >= 0, slot1, spare), t)
+    src.scatter_(0, torch.where(slot2 >= 0, slot2, spare), t)
+    src = src[:E * C]
+    if N > 0:
+        aux = E * (p.mean(dim=0) * (count1.to(p.dtype) / N)).sum()
+    else:
+        aux = p.new_zeros(())
+    i32 = torch.int32
+    return (w1, w2, idx1.to(i32), idx2.to(i32), slot1.to(i32),
+            slot2.to(i32), src.to(i32), aux, count1.to(i32))
+
+
+def moe_top2_route_bwd(logits, idx1, idx2, w1, w2, count1, dw1, dw2, daux):
+    """dlogits of (w1, w2, aux); count1 is a constant.
+    d aux / d p[t, e] = E * count1[e] / N^2, through the softmax;
+    dl1 = (dw1 - dw2) * w1 * w2 = -dl2 on the two chosen columns."""
+    lf = _up(logits)
+    N, E = lf.shape
+    p = torch.softmax(lf, dim=-1)
+    dp = (daux.to(p.dtype) * E / (N * N)) * count1.to(p.dtype)
+    dl = p * (dp - (p * dp).sum(dim=-1, keepdim=True))
+    dl1 = ((dw1 - dw2) * w1 * w2).to(p.dtype).unsqueeze(-1)
+    dl = dl.scatter_add(1, idx1.long().unsqueeze(-1), dl1)
+    dl = dl.scatter_add(1, idx2.long().unsqueeze(-1), -dl1)
+    return dl.to(logits.dtype)
+
+
+def _moe_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """x[idx] with zero rows where idx < 0 (fixed shape)."""
+    if x.shape[0] == 0:
+        return x.new_zeros(idx.shape[0], x.shape[1])
+    rows = x.index_select(0, idx.clamp_min(0).long())
+    return torch.where((idx >= 0).unsqueeze(-1), rows, torch.zeros_like(rows))
+
+
+def moe_dispatch(x: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+    """x [N, H], src [E*C] -> [E*C, H]: row s is x[src[s]], zeros if empty."""
+    return _moe_rows(x, src)
+
+
+def moe_combine(y: torch.Tensor, w1, w2, slot1: torch.Tensor,
+                slot2: torch.Tensor) -> torch.Tensor:
+    """out[t] = w1[t] * y[slot1[t]] + w2[t] * y[slot2[t]], dropped terms
+    skipped; summed in the upcast dtype and rounded once.  w1 = w2 = None
+    means unit weights, which makes this the backward of moe_dispatch."""
+    yf = _up(y)
+    a, b = _moe_rows(yf, slot1), _moe_rows(yf, slot2)
+    if w1 is not None:
+        # where, not a bare product: a dropped choice of a NaN-weighted
+        # token must contribute nothing
+        a = torch.where((slot1 >= 0).unsqueeze(-1),
+                        w1.to(yf.dtype).unsqueeze(-1) * a, a)
+        b = torch.where((slot2 >= 0).unsqueeze(-1),
+                        w2.to(yf.dtype).unsqueeze(-1) * b, b)
+    return (a + b).to(y.dtype)
+
+
+def moe_dispatch_bwd(g: torch.Tensor, slot1: torch.Tensor,
+                     slot2: torch.Tensor) -> torch.Tensor:
+    """dx[t] = g[slot1[t]] + g[slot2[t]]."""
+    return moe_combine(g, None, None, slot1, slot2)
+
+
+def moe_combine_bwd(dout: torch.Tensor, y: torch.Tensor, w1: torch.Tensor,
+                    w2: torch.Tensor, slot1: torch.Tensor,
+                    slot2: torch.Tensor, src: torch.Tensor):
+    """(dy, dw1, dw2): dy[s] = w_k * dout[src[s]] with k the choice that
+    owns slot s; dw_k[t] = <dout[t], y[slot_k[t]]>, 0 when dropped."""
+    df, yf = _up(dout), _up(y)
+    S = src.shape[0]
+    tok = src.clamp_min(0).long()
+    if dout.shape[0] == 0:
+        dy = torch.zeros_like(y)
+    else:
+        first = slot1.index_select(0, tok) == torch.arange(S,
+                                                           device=src.device)
+        scale = torch.where(first, w1.index_select(0, tok),
+                            w2.index_select(0, tok)).to(df.dtype)
+        rows = scale.unsqueeze(-1) * df.index_select(0, tok)
+        dy = torch.where((src >= 0).unsqueeze(-1), rows,
+                         torch.zeros_like(rows)).to(y.dtype)
+    dw1 = (df * _moe_rows(yf, slot1)).sum(-1).to(w1.dtype)
+    dw2 = (df * _moe_rows(yf, slot2)).sum(-1).to(w2.dtype)
+    return dy, dw1, dw2

@@ -19,6 +19,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from .. import ops
+from ..global_env import global_config
 from ..mesh import DeviceMesh, is_distributed
 from .layers import tag_seed
 
@@ -143,26 +145,36 @@ class ExpertParallelMLP(nn.Module):
         C = max(1, int(self.capacity_factor * N * 2 / self.E))
 
         logits = xf @ self.wg.to(xf.dtype)
-        w1g, i1, w2g, i2 = top2_gating(logits, C)
+        # GPU bf16: gate, slots, dispatch and combine on the HIP kernels,
+        # with fixed shapes and no device read-back.  Anything else (CPU,
+        # fp32, shapes outside the envelope) takes the torch ops below.
+        fused = global_config.moe_fused_routing and \
+            ops.moe_fused_ok(xf, self.E, C)
+        if fused:
+            routing = ops.moe_top2_route(logits, C)
+            self.last_aux_loss = routing.aux_loss
+            dispatched = ops.moe_dispatch(xf, routing)
+        else:
+            w1g, i1, w2g, i2 = top2_gating(logits, C)
 
-        # aux load-balance loss (GShard): E * sum(mean_prob * frac_top1)
-        gates = torch.softmax(logits.float(), dim=-1)
-        me = gates.mean(dim=0)
-        ce = torch.nn.functional.one_hot(i1, self.E).float().mean(dim=0)
-        self.last_aux_loss = self.E * (me * ce).sum()
+            # aux load-balance loss (GShard): E * sum(mean_prob * frac_top1)
+            gates = torch.softmax(logits.float(), dim=-1)
+            me = gates.mean(dim=0)
+            ce = torch.nn.functional.one_hot(i1, self.E).float().mean(dim=0)
+            self.last_aux_loss = self.E * (me * ce).sum()
 
-        zeros = torch.zeros(1, self.E, dtype=torch.long, device=x.device)
-        pos1, keep1, counts = self._assign_slots(i1, C, zeros)
-        pos2, keep2, _ = self._assign_slots(i2, C, counts)
+            zeros = torch.zeros(1, self.E, dtype=torch.long, device=x.device)
+            pos1, keep1, counts = self._assign_slots(i1, C, zeros)
+            pos2, keep2, _ = self._assign_slots(i2, C, counts)
 
-        t_all = torch.arange(N, device=x.device)
-        t_idx = torch.cat([t_all[keep1], t_all[keep2]])
-        flat_slot = torch.cat([(i1 * C + pos1)[keep1],
-                               (i2 * C + pos2)[keep2]])
-        gate_w = torch.cat([w1g[keep1], w2g[keep2]])
+            t_all = torch.arange(N, device=x.device)
+            t_idx = torch.cat([t_all[keep1], t_all[keep2]])
+            flat_slot = torch.cat([(i1 * C + pos1)[keep1],
+                                   (i2 * C + pos2)[keep2]])
+            gate_w = torch.cat([w1g[keep1], w2g[keep2]])
 
-        dispatched = xf.new_zeros(self.E * C, H)
-        dispatched.index_copy_(0, flat_slot, xf.index_select(0, t_idx))
+            dispatched = xf.new_zeros(self.E * C, H)
+            dispatched.index_copy_(0, flat_slot, xf.index_select(0, t_idx))
 
         # all-to-all: [E, C, H] blocks grouped by destination rank
         routed = all_to_all(dispatched.view(self.E, C, H), self.mesh,
@@ -191,6 +203,9 @@ class ExpertParallelMLP(nn.Module):
             .reshape(self.E, C, H)
         returned = all_to_all(h, self.mesh, self.axis)
 
+        if fused:
+            out = ops.moe_combine(returned.view(self.E * C, H), routing)
+            return out.reshape(B, S, H)
         out = xf.new_zeros(N, H)
         out.index_add_(0, t_idx,
                        returned.view(self.E * C, H)
