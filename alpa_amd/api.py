@@ -17,7 +17,7 @@ import torch
 from .global_env import global_config
 from .mesh import (DeviceMesh, device, init_distributed, is_distributed,
                    rank, shutdown as _mesh_shutdown, world_size)
-from .optim import AdamW
+from .optim import AdamW, check_max_grad_norm
 from .parallel.grad_sync import GradSynchronizer
 from .parallel_method import ParallelMethod, ShardParallel
 
@@ -54,14 +54,74 @@ class TrainState:
         #: unused for the default bf16 compute dtype
         self.dynamic_scale = None
 
+    @staticmethod
+    def _check_clip_supported(max_grad_norm: Optional[float],
+                              method: ParallelMethod,
+                              mesh: Optional[DeviceMesh]) -> None:
+        """Global-norm clipping needs the norm over every gradient of the
+        model exactly once.  Serial, dp and ZeRO-2/3 runs can form it, and
+        so can dp with expert parallelism (_expert_grad_groups); the
+        layouts below cannot yet, and fail here instead of clipping by a
+        wrong norm."""
+        if max_grad_norm is None:
+            return
+        from .parallel_method import PipeshardParallel
+        if isinstance(method, PipeshardParallel):
+            raise NotImplementedError(
+                "max_grad_norm is not supported with PipeshardParallel: each "
+                "stage holds only its own gradients and there is no "
+                "cross-stage reduction of their sum of squares yet")
+        if mesh is not None and mesh.axis_size(method.tp_axis) > 1:
+            raise NotImplementedError(
+                "max_grad_norm is not supported with tp > 1: there is no "
+                "registry yet of which parameters are TP-sharded (summed "
+                "over tp ranks) and which are replicated (counted once), "
+                "so the global gradient norm cannot be formed")
+
+    @staticmethod
+    def _expert_grad_groups(max_grad_norm: Optional[float],
+                            model: torch.nn.Module,
+                            method: ParallelMethod) -> dict:
+        """{id(param): process group} for expert-parallel weights whose
+        experts are spread over more than one rank.  Their gradients are
+        not all-reduced (each rank owns other experts), so the clipping
+        norm must sum their squares over that group, while every other
+        gradient is replicated and counts once.  The ZeRO optimizers shard
+        flat buckets without that distinction, so they refuse."""
+        if max_grad_norm is None:
+            return {}
+        from .parallel.expert import ExpertParallelMLP
+        groups = {}
+        for mod in model.modules():
+            if isinstance(mod, ExpertParallelMLP) and mod.ep > 1:
+                group = mod.mesh.axis_group(mod.axis)
+                for p in (mod.w1, mod.w2):
+                    groups[id(p)] = group
+        if groups and method.zero_stage >= 2:
+            raise NotImplementedError(
+                "max_grad_norm is not supported with expert parallelism "
+                "under ZeRO-2/3: the sharded optimizers cannot tell "
+                "rank-local expert gradients from replicated ones when "
+                "they form the global gradient norm")
+        return groups
+
     @classmethod
     def create(cls, model_fn, method: ParallelMethod, lr: float = 1e-4,
                betas=(0.9, 0.95), weight_decay: float = 0.0,
-               optimizer_cls=AdamW) -> "TrainState":
+               optimizer_cls=AdamW,
+               max_grad_norm: Optional[float] = None) -> "TrainState":
         """model_fn(mesh, axis, dtype, device) -> nn.Module built directly
         on the target device with method-resolved sharding; for
-        PipeshardParallel, model_fn is a PipelineModelSpec instead."""
+        PipeshardParallel, model_fn is a PipelineModelSpec instead.
+
+        ``max_grad_norm`` clips the gradients by their global norm inside
+        the fused AdamW step (optax ``clip_by_global_norm``); after a step
+        ``state.optimizer.last_grad_norm`` holds the pre-clip norm on the
+        device.  Supported for serial, dp (with or without expert
+        parallelism), ZeRO-2 and ZeRO-3 runs."""
         from .parallel_method import PipeshardParallel
+        check_max_grad_norm(max_grad_norm)
+        cls._check_clip_supported(max_grad_norm, method, None)
         if isinstance(method, PipeshardParallel):
             from .pipeline_parallel.compile import build_pipeline_state
             stage_module, engine, opt, gs, meshes = build_pipeline_state(
@@ -72,31 +132,43 @@ class TrainState:
             state.stage_meshes = meshes
             return state
         mesh = method.resolve_mesh()
+        cls._check_clip_supported(max_grad_norm, method, mesh)
         dtype = getattr(torch, global_config.compute_dtype) \
             if torch.cuda.is_available() else torch.float32
         model = model_fn(mesh=mesh, axis=method.tp_axis, dtype=dtype,
                          device=device())
+        expert_groups = cls._expert_grad_groups(max_grad_norm, model, method)
         state = cls(model, None, method, mesh)
         if method.zero_stage >= 3:
-            state._install_zero3(lr, betas, weight_decay)
+            state._install_zero3(lr, betas, weight_decay, max_grad_norm)
         elif method.zero_stage == 2:
             state._install_grad_sync()
             from .parallel.zero import ZeroOptimizer
             state.optimizer = ZeroOptimizer(state.grad_sync, lr=lr,
                                             betas=betas,
-                                            weight_decay=weight_decay)
+                                            weight_decay=weight_decay,
+                                            max_grad_norm=max_grad_norm)
         else:
             state._install_grad_sync()
+            # only pass the options where they are set: optimizer_cls may
+            # be a user class without them
+            clip = {}
+            if max_grad_norm is not None:
+                clip["max_grad_norm"] = max_grad_norm
+            if expert_groups:
+                clip["grad_norm_groups"] = expert_groups
             state.optimizer = optimizer_cls(model.parameters(), lr=lr,
                                             betas=betas,
-                                            weight_decay=weight_decay)
+                                            weight_decay=weight_decay,
+                                            **clip)
         return state
 
     @classmethod
     def create_auto(cls, builder: Callable[[], torch.nn.Module],
                     example_inputs, method: Optional["ShardParallel"] = None,
                     lr: float = 1e-4, betas=(0.9, 0.95),
-                    weight_decay: float = 0.0) -> "TrainState":
+                    weight_decay: float = 0.0,
+                    max_grad_norm: Optional[float] = None) -> "TrainState":
         """Automatic parallelization of an ARBITRARY plain torch module —
         no zoo membership, no model_hint (the reference's headline
         capability: trace any program and parallelize it,
@@ -111,8 +183,11 @@ class TrainState:
         (shard_parallel/plan_apply.py).  The usual step machinery
         (microbatching, overlapped grad sync, fused AdamW) is installed
         on top, so `aa.parallelize(step_fn)` works unchanged.
+        ``max_grad_norm`` is as in :meth:`create`; a plan that shards over
+        tp raises NotImplementedError.
         """
         from .shard_parallel import auto_shard
+        check_max_grad_norm(max_grad_norm)
         method = method or ShardParallel()
         model = builder()
         dtype = getattr(torch, global_config.compute_dtype) \
@@ -134,14 +209,18 @@ class TrainState:
             force_data_parallel=o.force_data_parallel,
             mesh_shape=method.logical_mesh_shape)
         method.logical_mesh_shape = plan.mesh_shape
+        cls._check_clip_supported(max_grad_norm, method, mesh)
+        expert_groups = cls._expert_grad_groups(max_grad_norm, model, method)
         state = cls(model, None, method, mesh)
         state.plan = plan
         state._install_grad_sync()
         state.optimizer = AdamW(model.parameters(), lr=lr, betas=betas,
-                                weight_decay=weight_decay)
+                                weight_decay=weight_decay,
+                                max_grad_norm=max_grad_norm,
+                                grad_norm_groups=expert_groups or None)
         return state
 
-    def _install_zero3(self, lr, betas, weight_decay):
+    def _install_zero3(self, lr, betas, weight_decay, max_grad_norm=None):
         """ZeRO-3: block params sharded + JIT-gathered (parallel/zero3.py);
         leftover params (e.g. positional embeddings) use plain DP sync."""
         from .parallel.zero3 import Zero3Manager, Zero3Optimizer
@@ -169,9 +248,11 @@ class TrainState:
                 if p.requires_grad and id(p) not in manager._by_param]
         self.grad_sync = GradSynchronizer(rest, self.mesh, axis=m.dp_axis)
         z3 = Zero3Optimizer(manager, lr=lr, betas=betas,
-                            weight_decay=weight_decay)
+                            weight_decay=weight_decay,
+                            max_grad_norm=max_grad_norm)
         rest_opt = AdamW(rest, lr=lr, betas=betas,
-                         weight_decay=weight_decay) if rest else None
+                         weight_decay=weight_decay,
+                         max_grad_norm=max_grad_norm) if rest else None
         state_self = self
 
         class _Composite:
@@ -182,11 +263,26 @@ class TrainState:
                 # sharded moments of both halves)
                 self.z3 = z3
                 self.rest_opt = rest_opt
+                self.max_grad_norm = max_grad_norm
+                self.last_grad_norm = None
 
-            def step(self, grads=None, grad_scale: float = 1.0):
-                z3.step(grad_scale=grad_scale)
+            def step(self, grads=None, grad_scale: float = 1.0,
+                     grad_sumsq=None):
+                if max_grad_norm is not None and grad_sumsq is None:
+                    # one global coefficient for both halves: the shards'
+                    # sum over dp plus the replicated rest's, counted once
+                    from . import ops
+                    grad_sumsq = z3.shard_sumsq()
+                    rest_grads = [p.grad for p in rest_opt.params
+                                  if p.grad is not None] if rest_opt else []
+                    if rest_grads:
+                        grad_sumsq = grad_sumsq + \
+                            ops.multi_tensor_sumsq(rest_grads)
+                z3.step(grad_scale=grad_scale, grad_sumsq=grad_sumsq)
                 if rest_opt is not None:
-                    rest_opt.step(grad_scale=grad_scale)
+                    rest_opt.step(grad_scale=grad_scale,
+                                  grad_sumsq=grad_sumsq)
+                self.last_grad_norm = z3.last_grad_norm
                 # shard grads accumulated across microbatches: clear for
                 # the next step
                 manager.zero_grads()

@@ -5,7 +5,8 @@ built from ``csrc/``); CPU tensors -> the pure-torch reference
 (`reference.py`).  Plain unfused GEMMs go through ``torch.matmul``
 (hipBLASLt on ROCm) — hand-written kernels cover the *fused* ops where
 library calls can't: LayerNorm, flash attention, bias+GeLU epilogue,
-softmax-cross-entropy over the 51200-wide vocab, multi-tensor AdamW, and
+softmax-cross-entropy over the 51200-wide vocab, multi-tensor AdamW with
+global-norm gradient clipping (multi_tensor_sumsq feeds fused_adamw), and
 the sync-free top-2 MoE routing path: moe_top2_route (gate + capacity
 slots), moe_dispatch and moe_combine.
 
@@ -26,6 +27,7 @@ from ._backend import hip_ops, hip_ops_available, use_hip
 __all__ = [
     "layer_norm", "add_layer_norm", "bias_gelu", "flash_attention",
     "flash_attention_qkv", "softmax_cross_entropy", "fused_adamw",
+    "multi_tensor_sumsq",
     "hip_ops_available", "MoERouting", "moe_top2_route", "moe_dispatch",
     "moe_combine", "moe_fused_ok",
 ]
@@ -391,6 +393,22 @@ _ADAM_CHUNK = 16384  # must match ADAM_CHUNK in csrc/adamw.hip
 _ADAM_TABLE_CACHE: dict = {}
 
 
+def _upload_tables(rows, dev):
+    """rows: (p, g, m, v, numel, is_bf16) per tensor, pointers as ints.
+    Returns the device-side descriptor table and the chunk table that maps
+    each workgroup to (tensor_idx, chunk_idx)."""
+    n = len(rows)
+    descs = torch.tensor(rows, dtype=torch.int64).reshape(n, 6)
+    counts = [(r[4] + _ADAM_CHUNK - 1) // _ADAM_CHUNK for r in rows]
+    tensor_idx = torch.repeat_interleave(
+        torch.arange(n, dtype=torch.int32),
+        torch.tensor(counts, dtype=torch.int64))
+    chunk_idx = torch.cat([torch.arange(c, dtype=torch.int32)
+                           for c in counts])
+    chunks = torch.stack([tensor_idx, chunk_idx], dim=1).contiguous()
+    return descs.to(dev), chunks.to(dev)
+
+
 def _adam_tables(params, grads, exp_avgs, exp_avg_sqs):
     """Build (and cache) the device-side tensor-descriptor + chunk tables
     consumed by the multi-tensor AdamW kernel (one launch per step)."""
@@ -404,32 +422,66 @@ def _adam_tables(params, grads, exp_avgs, exp_avg_sqs):
     hit = _ADAM_TABLE_CACHE.get(key)
     if hit is not None:
         return hit
-    n = len(params)
-    descs = torch.empty(n, 6, dtype=torch.int64)
-    counts = []
-    for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs,
-                                         exp_avg_sqs)):
+    rows = []
+    for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
         assert p.is_contiguous() and g.is_contiguous()
         assert m.dtype == torch.float32 and v.dtype == torch.float32
         assert p.dtype == g.dtype and p.dtype in (torch.bfloat16,
                                                   torch.float32)
-        descs[i, 0] = p.data_ptr()
-        descs[i, 1] = g.data_ptr()
-        descs[i, 2] = m.data_ptr()
-        descs[i, 3] = v.data_ptr()
-        descs[i, 4] = p.numel()
-        descs[i, 5] = 1 if p.dtype == torch.bfloat16 else 0
-        counts.append((p.numel() + _ADAM_CHUNK - 1) // _ADAM_CHUNK)
-    tensor_idx = torch.repeat_interleave(
-        torch.arange(n, dtype=torch.int32),
-        torch.tensor(counts, dtype=torch.int64))
-    chunk_idx = torch.cat([torch.arange(c, dtype=torch.int32)
-                           for c in counts])
-    chunks = torch.stack([tensor_idx, chunk_idx], dim=1).contiguous()
-    dev = params[0].device
-    tbl = (descs.to(dev), chunks.to(dev))
+        rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                     p.numel(), 1 if p.dtype == torch.bfloat16 else 0))
+    tbl = _upload_tables(rows, params[0].device)
     _ADAM_TABLE_CACHE[key] = tbl
     return tbl
+
+
+_SUMSQ_TABLE_CACHE: dict = {}
+
+
+def _sumsq_tables(tensors):
+    """Tables for the sum-of-squares kernels, in the AdamW layout with only
+    the g, numel and is_bf16 fields filled, plus the per-chunk fp32
+    workspace.  Built on the first call for a tensor list and cached, so
+    later calls copy nothing to the device."""
+    key = tuple((t.data_ptr(), t.numel(), t.dtype) for t in tensors)
+    hit = _SUMSQ_TABLE_CACHE.get(key)
+    if hit is not None:
+        return hit
+    rows = []
+    for t in tensors:
+        assert t.is_contiguous()
+        assert t.dtype in (torch.bfloat16, torch.float32)
+        rows.append((0, t.data_ptr(), 0, 0, t.numel(),
+                     1 if t.dtype == torch.bfloat16 else 0))
+    dev = tensors[0].device
+    descs, chunks = _upload_tables(rows, dev)
+    partials = torch.empty(chunks.shape[0], dtype=torch.float32, device=dev)
+    tbl = (descs, chunks, partials)
+    _SUMSQ_TABLE_CACHE[key] = tbl
+    return tbl
+
+
+@torch.no_grad()
+def multi_tensor_sumsq(tensors: List[torch.Tensor]) -> torch.Tensor:
+    """Sum of squares over every element of every tensor: fp32 [1] on the
+    tensors' device.  The list may mix bf16 and fp32; each tensor is
+    contiguous and may be a view at any element offset.
+
+    On the GPU this is one reduce launch plus one finalize launch, with a
+    fixed summation order (bit-reproducible) and no device read-back, so it
+    can sit inside a captured graph after one eager call has built the
+    cached tables.  The per-chunk workspace is shared by every call on the
+    same tensor list, so such calls belong on one stream.  Its sqrt is the
+    global norm that :func:`fused_adamw` clips by."""
+    tensors = [t for t in tensors if t.numel() > 0]
+    if not tensors:
+        raise ValueError("multi_tensor_sumsq needs at least one element")
+    if use_hip(tensors[0]):
+        descs, chunks, partials = _sumsq_tables(tensors)
+        out = torch.empty(1, dtype=torch.float32, device=tensors[0].device)
+        hip_ops().multi_tensor_sumsq_raw(descs, chunks, partials, out)
+        return out
+    return ref.multi_tensor_sumsq(tensors)
 
 
 @torch.no_grad()
@@ -437,23 +489,43 @@ def fused_adamw(params: List[torch.Tensor], grads: List[torch.Tensor],
                 exp_avgs: List[torch.Tensor], exp_avg_sqs: List[torch.Tensor],
                 step: int, lr: float, beta1: float = 0.9, beta2: float = 0.95,
                 eps: float = 1e-8, weight_decay: float = 0.0,
-                grad_scale: float = 1.0) -> None:
+                grad_scale: float = 1.0,
+                grad_sumsq: Optional[torch.Tensor] = None,
+                max_grad_norm: Optional[float] = None) -> None:
     """Multi-tensor AdamW update, in place — ONE kernel launch for all
     params.
 
     Params may be bf16 (fp32 master math happens inside the kernel against
     the fp32 exp_avg/exp_avg_sq state).  Analog of the fused Adam the
     reference gets inside its apply_grad HLO.
+
+    Global-norm clipping (optax ``clip_by_global_norm``): give both
+    ``grad_sumsq``, the fp32 [1] sum of squares of ALL gradients of the
+    model (:func:`multi_tensor_sumsq`, summed over ranks where gradients
+    are sharded), and ``max_grad_norm``.  The gradients are then scaled by
+    ``grad_scale * max_grad_norm / max(norm, max_grad_norm)`` with
+    ``norm = |grad_scale| * sqrt(grad_sumsq)``, inside the kernel: the
+    coefficient never leaves the device.  If the norm is not finite the
+    call changes nothing — params and moments keep their values — though
+    the caller's step counter has moved on.  bf16 gradients above about
+    1.8e19 overflow the fp32 square and count as non-finite.
     """
+    if (grad_sumsq is None) != (max_grad_norm is None):
+        raise ValueError(
+            "grad_sumsq and max_grad_norm must be given together")
+    if max_grad_norm is not None and not max_grad_norm > 0:
+        raise ValueError(f"max_grad_norm must be > 0, got {max_grad_norm}")
     if not params:
         return
     if use_hip(params[0]):
         descs, chunks = _adam_tables(params, grads, exp_avgs, exp_avg_sqs)
         hip_ops().adamw_step_raw(descs, chunks, step, lr, beta1, beta2, eps,
-                                 weight_decay, grad_scale)
+                                 weight_decay, grad_scale, grad_sumsq,
+                                 max_grad_norm or 0.0)
     else:
         ref.adamw_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1,
-                       beta2, eps, weight_decay, grad_scale)
+                       beta2, eps, weight_decay, grad_scale, grad_sumsq,
+                       max_grad_norm)
 
 
 # ------------------------------- MoE routing -------------------------------

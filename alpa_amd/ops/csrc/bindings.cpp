@@ -289,12 +289,42 @@ at::Tensor skinny_gemm(const at::Tensor& wp, const at::Tensor& x,
 
 void adamw_step_raw(const at::Tensor& descs, const at::Tensor& chunks,
                     int64_t step, double lr, double beta1, double beta2,
-                    double eps, double weight_decay, double grad_scale) {
+                    double eps, double weight_decay, double grad_scale,
+                    const c10::optional<at::Tensor>& grad_sumsq,
+                    double max_grad_norm) {
   TORCH_CHECK(descs.is_cuda() && chunks.is_cuda());
+  const float* sumsq = nullptr;
+  if (grad_sumsq.has_value()) {
+    TORCH_CHECK(grad_sumsq->is_cuda(), "grad_sumsq must be on GPU");
+    TORCH_CHECK(grad_sumsq->scalar_type() == at::kFloat,
+                "grad_sumsq must be fp32");
+    TORCH_CHECK(grad_sumsq->numel() == 1, "grad_sumsq must have 1 element");
+    TORCH_CHECK(max_grad_norm > 0, "max_grad_norm must be positive");
+    sumsq = (const float*)grad_sumsq->const_data_ptr();
+  }
   HIP_OK(launch_adamw(descs.const_data_ptr(), chunks.const_data_ptr(),
                       (int)chunks.size(0), (float)lr, (float)beta1,
                       (float)beta2, (float)eps, (float)weight_decay,
-                      (float)grad_scale, (int)step, cur_stream()));
+                      (float)grad_scale, (int)step, sumsq,
+                      (float)max_grad_norm, cur_stream()));
+}
+
+// descs/chunks: the AdamW tables (only g, numel and is_bf16 are read);
+// partials: fp32 workspace [num_chunks]; out: fp32 [1]
+void multi_tensor_sumsq_raw(const at::Tensor& descs, const at::Tensor& chunks,
+                            at::Tensor& partials, at::Tensor& out) {
+  TORCH_CHECK(descs.is_cuda() && chunks.is_cuda());
+  int64_t n = chunks.size(0);
+  TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
+                  partials.is_contiguous() && partials.numel() >= n,
+              "partials must be fp32 [num_chunks] on GPU");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat &&
+                  out.numel() == 1,
+              "out must be fp32 [1] on GPU");
+  HIP_OK(launch_multi_tensor_sumsq(
+      descs.const_data_ptr(), chunks.const_data_ptr(), (int)n,
+      (float*)partials.mutable_data_ptr(), (float*)out.mutable_data_ptr(),
+      cur_stream()));
 }
 
 // ----------------------------- CrossEntropy ------------------------------
@@ -772,7 +802,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // attn_fwd_ablate, attn_bwd_dkv_ablate) were removed
   // 4: MoE routing entries (moe_route_fwd/bwd, moe_dispatch, moe_combine,
   // moe_combine_dw) added
-  m.attr("ABI_VERSION") = 4;
+  // 5: multi_tensor_sumsq_raw added; adamw_step_raw takes grad_sumsq and
+  // max_grad_norm
+  m.attr("ABI_VERSION") = 5;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)");
   m.def("add_layer_norm_fwd", &add_layer_norm_fwd,
@@ -784,7 +816,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("colsum_bf16", &colsum_bf16, "striped column sum (gfx950)");
   m.def("skinny_gemm", &skinny_gemm,
         "decode GEMV over packed weights (gfx950)");
-  m.def("adamw_step_raw", &adamw_step_raw, "multi-tensor AdamW (gfx950)");
+  m.def("adamw_step_raw", &adamw_step_raw, "multi-tensor AdamW (gfx950)",
+        py::arg("descs"), py::arg("chunks"), py::arg("step"), py::arg("lr"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("weight_decay"), py::arg("grad_scale"),
+        py::arg("grad_sumsq") = py::none(), py::arg("max_grad_norm") = 0.0);
+  m.def("multi_tensor_sumsq_raw", &multi_tensor_sumsq_raw,
+        "multi-tensor sum of squares (gfx950)");
   m.def("fp8_quantize", &fp8_quantize,
         "one-pass fp8 amax+cast, optional transposed twin (gfx950)");
   m.def("cross_entropy_fwd", &cross_entropy_fwd, "fused CE fwd (gfx950)");

@@ -50,7 +50,14 @@ hipError_t launch_colsum_partial(const void* t, float* part, int64_t N,
 hipError_t launch_adamw(const void* descs_dev, const void* chunks_dev,
                         int num_chunks, float lr, float beta1, float beta2,
                         float eps, float weight_decay, float grad_scale,
-                        int step, hipStream_t stream);
+                        int step, const float* sumsq_or_null, float max_norm,
+                        hipStream_t stream);
+// sum of squares of every gradient in the table: one fp32 partial per chunk
+// into partials [num_chunks], then their fixed-order sum into sumsq [1]
+hipError_t launch_multi_tensor_sumsq(const void* descs_dev,
+                                     const void* chunks_dev, int num_chunks,
+                                     float* partials, float* sumsq,
+                                     hipStream_t stream);
 
 // ---- fp8_quant.hip ----
 hipError_t launch_fp8_quantize(const void* src, void* q, const float* scale,

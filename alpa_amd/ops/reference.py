@@ -196,19 +196,61 @@ def softmax_cross_entropy_bwd(dloss: torch.Tensor, logits: torch.Tensor,
 
 def adamw_step(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float,
                beta1: float, beta2: float, eps: float, weight_decay: float,
-               grad_scale: float = 1.0):
-    """In-place multi-tensor AdamW (fp32 master math on fp32 state)."""
+               grad_scale: float = 1.0, grad_sumsq=None,
+               max_grad_norm=None):
+    """In-place multi-tensor AdamW (fp32 master math on fp32 state).
+
+    With grad_sumsq (a one-element tensor, the sum of squares of all raw
+    gradients) and max_grad_norm, the gradients are clipped by global norm
+    as optax.clip_by_global_norm does: scaled by grad_scale * max_grad_norm
+    / max(norm, max_grad_norm), norm = |grad_scale| * sqrt(grad_sumsq).
+    The clip math runs in grad_sumsq's dtype.  A non-finite norm leaves
+    params and moments as they were; like the kernel, this is decided by
+    torch.where on tensors and never by a host branch on tensor data."""
+    if (grad_sumsq is None) != (max_grad_norm is None):
+        raise ValueError(
+            "grad_sumsq and max_grad_norm must be given together")
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
+    if grad_sumsq is None:
+        for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
+            gf = _up(g) * grad_scale
+            pf = _up(p)
+            pf.mul_(1.0 - lr * weight_decay)
+            m.mul_(beta1).add_(gf, alpha=1.0 - beta1)
+            v.mul_(beta2).addcmul_(gf, gf, value=1.0 - beta2)
+            denom = (v / bc2).sqrt_().add_(eps)
+            pf.addcdiv_(m / bc1, denom, value=-lr)
+            p.copy_(pf.to(p.dtype))
+        return
+    if not max_grad_norm > 0:
+        raise ValueError(f"max_grad_norm must be > 0, got {max_grad_norm}")
+    norm = abs(grad_scale) * _up(grad_sumsq).reshape(()).sqrt()
+    ok = torch.isfinite(norm)
+    limit = torch.full_like(norm, max_grad_norm)
+    scale = grad_scale * (limit / torch.maximum(norm, limit))
     for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
-        gf = _up(g) * grad_scale
-        pf = _up(p)
-        pf.mul_(1.0 - lr * weight_decay)
-        m.mul_(beta1).add_(gf, alpha=1.0 - beta1)
-        v.mul_(beta2).addcmul_(gf, gf, value=1.0 - beta2)
-        denom = (v / bc2).sqrt_().add_(eps)
-        pf.addcdiv_(m / bc1, denom, value=-lr)
-        p.copy_(pf.to(p.dtype))
+        gf = _up(g) * scale.to(m.dtype)
+        # the unclipped update above, op for op, on copies
+        pf = _up(p).clone().mul_(1.0 - lr * weight_decay)
+        m_new = m.clone().mul_(beta1).add_(gf, alpha=1.0 - beta1)
+        v_new = v.clone().mul_(beta2).addcmul_(gf, gf, value=1.0 - beta2)
+        denom = (v_new / bc2).sqrt_().add_(eps)
+        pf.addcdiv_(m_new / bc1, denom, value=-lr)
+        m.copy_(torch.where(ok, m_new, m))
+        v.copy_(torch.where(ok, v_new, v))
+        p.copy_(torch.where(ok, pf.to(p.dtype), p))
+
+
+def multi_tensor_sumsq(tensors) -> torch.Tensor:
+    """Sum of squares over all elements of all tensors, shape [1]: fp32
+    (half precision is upcast), or fp64 if the tensors are."""
+    total = None
+    for t in tensors:
+        tf = _up(t).reshape(-1)
+        s = (tf * tf).sum()
+        total = s if total is None else total + s
+    return total.reshape(1)
 
 
 # ------------------------------ MoE routing --------------------------------

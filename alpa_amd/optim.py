@@ -16,6 +16,21 @@ import torch
 from . import ops
 
 
+def check_max_grad_norm(max_grad_norm: Optional[float]) -> Optional[float]:
+    if max_grad_norm is not None and not max_grad_norm > 0:
+        raise ValueError(f"max_grad_norm must be > 0, got {max_grad_norm}")
+    return max_grad_norm
+
+
+def global_grad_norm(grad_sumsq: torch.Tensor,
+                     grad_scale: float) -> torch.Tensor:
+    """The pre-clip global norm of the gradients a step applies, as
+    torch.nn.utils.clip_grad_norm_ would return it: grad_sumsq is over the
+    raw gradients, which the step multiplies by grad_scale.  Stays on the
+    device."""
+    return abs(grad_scale) * grad_sumsq.sqrt()
+
+
 class AdamW:
     """Minimal AdamW over an explicit param list.
 
@@ -28,11 +43,29 @@ class AdamW:
     for its first real updates.  Training steps through `parallelize`
     always populate every grad via the bucket views, so the deviation
     only affects the raw-optimizer path with genuinely unused params.
+
+    `max_grad_norm` turns on global-norm gradient clipping (optax
+    ``clip_by_global_norm``) inside the fused kernel: one extra read of the
+    gradients and no write pass.  `step()` then computes the gradients' sum
+    of squares itself unless the caller passes `grad_sumsq` (a caller that
+    holds only part of the model's gradients here must pass the global
+    one), and leaves the pre-clip norm in `last_grad_norm`, a device
+    tensor.  A step whose norm is not finite changes no parameter and no
+    moment, but `step_count` still advances.  `grad_norm_groups` maps
+    id(param) to the process group over which that parameter's gradient is
+    sharded instead of replicated (expert-parallel weights): the squares of
+    those gradients are summed over the group, all others count once, so
+    every rank clips by the same global norm.
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-4,
                  betas=(0.9, 0.95), eps: float = 1e-8,
-                 weight_decay: float = 0.01):
+                 weight_decay: float = 0.01,
+                 max_grad_norm: Optional[float] = None,
+                 grad_norm_groups: Optional[dict] = None):
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self.grad_norm_groups = grad_norm_groups or {}
+        self.last_grad_norm: Optional[torch.Tensor] = None
         self.params: List[torch.nn.Parameter] = [
             p for p in params if p.requires_grad
         ]
@@ -52,7 +85,8 @@ class AdamW:
 
     @torch.no_grad()
     def step(self, grads: Optional[List[torch.Tensor]] = None,
-             grad_scale: float = 1.0):
+             grad_scale: float = 1.0,
+             grad_sumsq: Optional[torch.Tensor] = None):
         if grads is None:
             grads = [p.grad for p in self.params]
         self.step_count += 1
@@ -66,9 +100,36 @@ class AdamW:
         if not quads:
             return
         ps, gs, ms, vs = (list(t) for t in zip(*quads))
+        if self.max_grad_norm is not None:
+            if grad_sumsq is None:
+                grad_sumsq = self._global_sumsq(ps, gs)
+            self.last_grad_norm = global_grad_norm(grad_sumsq, grad_scale)
         ops.fused_adamw(ps, gs, ms, vs, self.step_count, self.lr,
                         self.beta1, self.beta2, self.eps,
-                        self.weight_decay, grad_scale)
+                        self.weight_decay, grad_scale, grad_sumsq,
+                        self.max_grad_norm)
+
+    def _global_sumsq(self, ps, gs) -> torch.Tensor:
+        """Sum of squares of the model's gradients: the replicated ones
+        once, plus each grad_norm_groups group's, all-reduced over it."""
+        if not self.grad_norm_groups:
+            return ops.multi_tensor_sumsq(gs)
+        from .mesh import is_distributed
+        shared, sharded = [], {}
+        for p, g in zip(ps, gs):
+            group = self.grad_norm_groups.get(id(p))
+            if group is None:
+                shared.append(g)
+            else:
+                sharded.setdefault(id(group), (group, []))[1].append(g)
+        total = ops.multi_tensor_sumsq(shared) if shared else None
+        for group, grads in sharded.values():
+            part = ops.multi_tensor_sumsq(grads)
+            if is_distributed():
+                torch.distributed.all_reduce(
+                    part, op=torch.distributed.ReduceOp.SUM, group=group)
+            total = part if total is None else total + part
+        return total
 
     def step_sharded(self, grad_sync, grad_scale: float = 1.0):
         """ZeRO-2 path: installed by parallel/zero.py (sharded state over

@@ -20,15 +20,24 @@ import torch.distributed as dist
 
 from .. import ops
 from ..mesh import is_distributed
+from ..optim import check_max_grad_norm, global_grad_norm
 from .grad_sync import GradSynchronizer
 
 
 class ZeroOptimizer:
-    """Sharded AdamW over GradSynchronizer's reduce-scatter buckets."""
+    """Sharded AdamW over GradSynchronizer's reduce-scatter buckets.
+
+    `max_grad_norm` clips by the global gradient norm (see optim.AdamW):
+    each rank sums the squares of its own 1/dp of every bucket and the sums
+    are all-reduced over dp, so every rank applies one coefficient.  Bucket
+    padding is zero and adds nothing."""
 
     def __init__(self, grad_sync: GradSynchronizer, lr: float = 1e-4,
                  betas=(0.9, 0.95), eps: float = 1e-8,
-                 weight_decay: float = 0.0):
+                 weight_decay: float = 0.0,
+                 max_grad_norm: Optional[float] = None):
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self.last_grad_norm: Optional[torch.Tensor] = None
         self.gs = grad_sync
         self.lr = lr
         self.beta1, self.beta2 = betas
@@ -103,14 +112,23 @@ class ZeroOptimizer:
         return out
 
     @torch.no_grad()
-    def step(self, grads=None, grad_scale: float = 1.0):
+    def step(self, grads=None, grad_scale: float = 1.0,
+             grad_sumsq: Optional[torch.Tensor] = None):
         self.step_count += 1
         from ..ops import fp8 as _fp8
         _fp8.bump_epoch()  # invalidate fp8 quantized-weight caches
+        if self.max_grad_norm is not None:
+            if grad_sumsq is None:
+                grad_sumsq = ops.multi_tensor_sumsq(self.grad_shards)
+                if self.gs.reduce_scatter and is_distributed():
+                    dist.all_reduce(
+                        grad_sumsq, op=dist.ReduceOp.SUM,
+                        group=self.gs.mesh.axis_group(self.gs.axis))
+            self.last_grad_norm = global_grad_norm(grad_sumsq, grad_scale)
         ops.fused_adamw(self.param_shards, self.grad_shards, self.exp_avgs,
                         self.exp_avg_sqs, self.step_count, self.lr,
                         self.beta1, self.beta2, self.eps, self.weight_decay,
-                        grad_scale)
+                        grad_scale, grad_sumsq, self.max_grad_norm)
         # all-gather updated params per bucket
         if self.gs.reduce_scatter and is_distributed():
             group = self.gs.mesh.axis_group(self.gs.axis)

@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..mesh import DeviceMesh, is_distributed
+from ..optim import check_max_grad_norm, global_grad_norm
 
 
 class _BlockShard:
@@ -196,11 +197,19 @@ class Zero3Manager:
 
 
 class Zero3Optimizer:
-    """Fused AdamW over the ZeRO-3 shard set."""
+    """Fused AdamW over the ZeRO-3 shard set.
+
+    `max_grad_norm` clips by the global gradient norm (see optim.AdamW).
+    The shards' sum of squares is all-reduced over dp; a caller that also
+    trains parameters outside the shard set adds theirs to
+    `shard_sumsq()` and passes the total as `grad_sumsq`."""
 
     def __init__(self, manager: Zero3Manager, lr: float = 1e-4,
                  betas=(0.9, 0.95), eps: float = 1e-8,
-                 weight_decay: float = 0.0):
+                 weight_decay: float = 0.0,
+                 max_grad_norm: Optional[float] = None):
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self.last_grad_norm: Optional[torch.Tensor] = None
         self.m = manager
         self.lr = lr
         self.beta1, self.beta2 = betas
@@ -229,14 +238,30 @@ class Zero3Optimizer:
         return out
 
     @torch.no_grad()
-    def step(self, grads=None, grad_scale: float = 1.0):
+    def shard_sumsq(self) -> torch.Tensor:
+        """Sum of squares of every rank's gradient shards: the local sum,
+        all-reduced over dp (shard padding is zero)."""
+        _, gshards = self.m.shards()
+        sumsq = ops.multi_tensor_sumsq(gshards)
+        if is_distributed() and self.m.group is not None and self.m.dp > 1:
+            dist.all_reduce(sumsq, op=dist.ReduceOp.SUM, group=self.m.group)
+        return sumsq
+
+    @torch.no_grad()
+    def step(self, grads=None, grad_scale: float = 1.0,
+             grad_sumsq: Optional[torch.Tensor] = None):
         self.step_count += 1
         from ..ops import fp8 as _fp8
         _fp8.bump_epoch()  # invalidate fp8 quantized-weight caches
         pshards, gshards = self.m.shards()
+        if self.max_grad_norm is not None:
+            if grad_sumsq is None:
+                grad_sumsq = self.shard_sumsq()
+            self.last_grad_norm = global_grad_norm(grad_sumsq, grad_scale)
         ops.fused_adamw(pshards, gshards, self.exp_avgs, self.exp_avg_sqs,
                         self.step_count, self.lr, self.beta1, self.beta2,
-                        self.eps, self.weight_decay, grad_scale)
+                        self.eps, self.weight_decay, grad_scale, grad_sumsq,
+                        self.max_grad_norm)
 
     def zero_grad(self):
         self.m.zero_grads()
