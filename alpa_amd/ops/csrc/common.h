@@ -81,6 +81,17 @@ __device__ __forceinline__ float block_reduce_max(float v, float* buf) {
   return r;
 }
 
+// XCD-aware workgroup swizzle (gfx950: 8 XCDs, hardware assigns
+// workgroup i to XCD i%8, each XCD has its own L2): remap so each XCD
+// gets a CONTIGUOUS run of logical blocks — all attention blocks of one
+// (batch,head) then share one L2 and its K/V (fwd) / Q,dO (bwd) tiles
+// are loaded from HBM once per XCD instead of once per block.
+__device__ inline int xcd_swizzle(int flat, int total) {
+  constexpr int NXCD = 8;
+  if (total % NXCD != 0) return flat;
+  return (flat % NXCD) * (total / NXCD) + flat / NXCD;
+}
+
 __host__ __forceinline__ int64_t ceil_div(int64_t a, int64_t b) {
   return (a + b - 1) / b;
 }
