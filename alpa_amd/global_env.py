@@ -59,6 +59,15 @@ class GlobalConfig:
     fp8_dx_bf16: bool = field(
         default_factory=lambda: os.environ.get("ALPA_AMD_FP8_DX_BF16",
                                                "0") == "1")
+    #: emit the fp8 GEMM operands straight from the LayerNorm and
+    #: bias+GeLU forward kernels (ops/csrc/fp8_fused.hip) instead of
+    #: writing the bf16 activation and quantizing it in a second pass.
+    #: Taken only under fp8_gemm with fp8_wgrad on and grad mode on;
+    #: bit-identical to the two-pass path and measured faster (GPT-2.6B
+    #: fp8 step 435 -> 426 ms, docs/BENCHMARK.md), so on by default.
+    #: ALPA_AMD_FP8_FUSED_QUANT=0 keeps the two-pass path
+    fp8_fused_quant: bool = field(
+        default_factory=lambda: _env_bool("ALPA_AMD_FP8_FUSED_QUANT", True))
     #: route MoE tokens through the fused HIP kernels (top-2 gate, capacity
     #: slots, dispatch, combine; ops/csrc/moe_route.hip) when the input is
     #: inside their envelope (ops.moe_fused_ok).  They never read the

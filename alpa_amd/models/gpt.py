@@ -86,6 +86,9 @@ def _wpe_init(cfg, dtype, device, init_seed: int):
     return w.to(dtype=dtype, device=device)
 
 
+_PLAIN = object()  # forward() sentinel: single-arg plain-path call
+
+
 class Attention(nn.Module):
     """Multi-head attention: fused qkv column-split by heads over the tp
     axis, flash-attention kernel, output row-split + all-reduce."""
@@ -107,12 +110,19 @@ class Attention(nn.Module):
                                      init_seed=init_seed,
                                      init_tag=f"b{layer_idx}.out")
 
-    def forward(self, x):
+    def forward(self, x, delta=_PLAIN, ln=None):
+        """Single-arg: attention on a normalized input.  With (res, delta,
+        ln): the residual add and LayerNorm `ln` run in front of the qkv
+        projection (fused into it where the fp8 fused-quantize route is
+        open) and (h, out) comes back, h = res + delta."""
         # packed per-head [q|k|v] projection; the strided attention kernel
         # consumes/produces these layouts directly (no permute copies)
-        qkv = self.qkv(x)  # [B, S, 3*H/tp]
+        if delta is _PLAIN:
+            qkv = self.qkv(x)  # [B, S, 3*H/tp]
+        else:
+            h, qkv = self.qkv(x, delta, ln)
         o = ops.flash_attention_qkv(qkv, self.heads_per_rank, causal=True)
-        return self.out(o)
+        return self.out(o) if delta is _PLAIN else (h, self.out(o))
 
 
 class MLP(nn.Module):
@@ -130,11 +140,29 @@ class MLP(nn.Module):
                                      init_seed=init_seed,
                                      init_tag=f"b{layer_idx}.fc2")
 
-    def forward(self, x):
-        return self.fc2(self.fc1(x))
+    def forward(self, x, delta=_PLAIN, ln=None):
+        """Single-arg: the MLP on a normalized input.  With (res, delta,
+        ln): residual add + LayerNorm `ln` in front, returns (h, out).
+        Under the fp8 fused-quantize flag fc1 hands its GEMM output to
+        fc2, whose quantize kernel applies fc1's bias and GeLU."""
+        defer = _fused_quant_route()
+        if delta is _PLAIN:
+            h, pre = None, self.fc1(x, defer_gelu=defer)
+        else:
+            h, pre = self.fc1(x, delta, ln, defer_gelu=defer)
+        out = self.fc2(pre, gelu_bias=self.fc1.bias) if defer \
+            else self.fc2(pre)
+        return out if delta is _PLAIN else (h, out)
 
 
-_PLAIN = object()  # forward() sentinel: single-arg plain-path call
+def _fused_quant_route() -> bool:
+    """Coarse gate of the fp8 fused-quantize joins (LayerNorm -> qkv/fc1,
+    GeLU -> fc2).  The consuming linear makes the exact decision
+    (parallel.layers._fp8_fused_quant_ok) and otherwise runs the same
+    ops.add_layer_norm / ops.bias_gelu as the unfused route."""
+    from ..global_env import global_config
+    return (global_config.fp8_fused_quant and global_config.fp8_gemm
+            and global_config.fp8_wgrad and torch.is_grad_enabled())
 
 
 class LayerNorm(nn.Module):
@@ -186,12 +214,18 @@ class Block(nn.Module):
         """Residual-threaded form: both residual adds fuse into the
         LayerNorm kernels (ops.add_layer_norm).  Returns the next
         (residual, delta) pair; the stream value is res + delta."""
-        h, y1 = ops.add_layer_norm(res, delta, self.ln1.weight,
-                                   self.ln1.bias, self.ln1.eps)
-        a = self.attn(y1)
-        h2, y2 = ops.add_layer_norm(h, a, self.ln2.weight, self.ln2.bias,
-                                    self.ln2.eps)
-        return h2, self.mlp(y2)
+        if not _fused_quant_route():
+            h, y1 = ops.add_layer_norm(res, delta, self.ln1.weight,
+                                       self.ln1.bias, self.ln1.eps)
+            a = self.attn(y1)
+            h2, y2 = ops.add_layer_norm(h, a, self.ln2.weight,
+                                        self.ln2.bias, self.ln2.eps)
+            return h2, self.mlp(y2)
+        # fp8 fused quantize: each LayerNorm travels with the linear that
+        # consumes it (qkv, fc1), which runs it inside its quantize kernel
+        # or, outside that route, as the same ops.add_layer_norm
+        h, a = self.attn(res, delta, self.ln1)
+        return self.mlp(h, a, self.ln2)
 
 
 def _run_block(blk, res, delta, remat: bool):

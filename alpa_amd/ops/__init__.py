@@ -8,7 +8,9 @@ library calls can't: LayerNorm, flash attention, bias+GeLU epilogue,
 softmax-cross-entropy over the 51200-wide vocab, multi-tensor AdamW with
 global-norm gradient clipping (multi_tensor_sumsq feeds fused_adamw), and
 the sync-free top-2 MoE routing path: moe_top2_route (gate + capacity
-slots), moe_dispatch and moe_combine.
+slots), moe_dispatch and moe_combine.  add_layer_norm_fp8 and bias_gelu_fp8
+are the LayerNorm and GeLU forwards with the fp8 quantize of ops/fp8.py
+folded in.
 
 Kernel-level contract mirrors the reference's compiled-HLO op inventory
 (GEMM+epilogue, attention, LayerNorm, fused Adam,
@@ -25,7 +27,8 @@ from . import reference as ref
 from ._backend import hip_ops, hip_ops_available, use_hip
 
 __all__ = [
-    "layer_norm", "add_layer_norm", "bias_gelu", "flash_attention",
+    "layer_norm", "add_layer_norm", "bias_gelu", "add_layer_norm_fp8",
+    "bias_gelu_fp8", "flash_attention",
     "flash_attention_qkv", "softmax_cross_entropy", "fused_adamw",
     "multi_tensor_sumsq",
     "hip_ops_available", "MoERouting", "moe_top2_route", "moe_dispatch",
@@ -128,6 +131,44 @@ class _BiasGelu(torch.autograd.Function):
 def bias_gelu(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """Fused (x + bias) -> gelu_tanh. The epilogue of the MLP up-projection."""
     return _BiasGelu.apply(x, bias)
+
+
+@torch.no_grad()
+def bias_gelu_fp8(x: torch.Tensor, bias: torch.Tensor, scale: torch.Tensor):
+    """gelu(x + bias) quantized straight to e4m3 for an fp8 GEMM, without
+    writing the bf16 activation: (q [N, F], qt [F, N], amax fp32 [1]) for
+    x [.., F], N = x.numel() / F.  `scale` is the delayed per-tensor scale
+    (fp32 [1] on x's device), amax the largest |gelu(x + bias)| after
+    rounding to bf16.  On the GPU the result is byte-for-byte that of
+    bias_gelu followed by the dual-layout quantize kernel.  Forward only:
+    ops.fp8.fp8_gelu_linear is the autograd user."""
+    x = x.contiguous()
+    if use_hip(x):
+        return tuple(hip_ops().bias_gelu_fp8(x, bias, scale))
+    return ref.bias_gelu_fp8(x, bias, scale)
+
+
+#: widest row ops.add_layer_norm_fp8 takes on the GPU: its kernel parks 16
+#: rows of fp8 bytes in 64 KB of LDS (FLN_MAX_H in csrc/fp8_fused.hip)
+ADD_LAYER_NORM_FP8_MAX_H = 4096
+
+
+@torch.no_grad()
+def add_layer_norm_fp8(a: torch.Tensor, delta, weight: torch.Tensor,
+                       bias: torch.Tensor, eps: float, scale: torch.Tensor):
+    """h = a (+ delta); LN(h) quantized straight to e4m3 for an fp8 GEMM,
+    without writing the bf16 normalized tensor: (h, mean [N], rstd [N],
+    q [N, H], qt [H, N], amax fp32 [1]).  delta may be None (h is then a
+    copy of a).  On the GPU the result is byte-for-byte that of
+    add_layer_norm followed by the dual-layout quantize kernel, and H is
+    at most ADD_LAYER_NORM_FP8_MAX_H.  Forward only: ops.fp8.fp8_ln_linear
+    is the autograd user."""
+    a = a.contiguous()
+    delta = delta.contiguous() if delta is not None else None
+    if use_hip(a):
+        return tuple(hip_ops().add_layer_norm_fp8(a, delta, weight, bias,
+                                                  eps, scale))
+    return ref.add_layer_norm_fp8(a, delta, weight, bias, eps, scale)
 
 
 class _BiasAdd(torch.autograd.Function):

@@ -5,22 +5,8 @@
 // bf16x8 vector loads, grid-stride, dbias via deterministic striped
 // partials + column sum.
 #include "common.h"
+#include "fused_math.h"  // gelu_sigmoid, gelu_f
 #include "launchers.h"
-
-// tanh-GeLU via the sigmoid identity: 0.5x(1+tanh(z)) == x*sigmoid(2z),
-// evaluated with ONE hardware __expf instead of libm tanhf (the tanh
-// path ran the elementwise kernels 1.7-1.9x off the HBM roofline —
-// VALU-bound on the polynomial tanh expansion).  Same function, only
-// the evaluation differs; bf16 outputs agree to rounding.
-__device__ __forceinline__ float gelu_sigmoid(float x) {
-  const float k2 = 2.0f * 0.7978845608028654f;
-  float z2 = k2 * (x + 0.044715f * x * x * x);
-  return 1.0f / (1.0f + __expf(-z2));
-}
-
-__device__ __forceinline__ float gelu_f(float x) {
-  return x * gelu_sigmoid(x);
-}
 
 __device__ __forceinline__ float gelu_grad_f(float x) {
   const float k = 0.7978845608028654f;

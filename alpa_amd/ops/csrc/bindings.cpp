@@ -793,6 +793,81 @@ std::vector<at::Tensor> fp8_quantize(const at::Tensor& x,
   return {q, qt, amax};
 }
 
+// ---------------------- producers fused with quantize ----------------------
+
+// previous-step delayed scale: one fp32 element on the device
+void check_fp8_scale(const at::Tensor& scale) {
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat &&
+              scale.numel() == 1, "scale must be a device fp32 scalar");
+}
+
+// row tiles (64 rows) ride on grid.y, which holds at most 65535
+constexpr int64_t kFusedQuantMaxRows = int64_t(1) << 21;
+
+// gelu(x + bias) quantized to e4m3 in both layouts, no bf16 output:
+// x [.., F] bf16 -> (q [N, F], qt [F, N], amax [1]), byte-equal to
+// bias_gelu_fwd followed by fp8_quantize(y, scale, dual, e4m3)
+std::vector<at::Tensor> bias_gelu_fp8(const at::Tensor& x,
+                                      const at::Tensor& bias,
+                                      const at::Tensor& scale) {
+  check_bf16_contig(x, "x");
+  TORCH_CHECK(x.dim() >= 1, "x must have a feature dimension");
+  int64_t F = x.size(-1);
+  TORCH_CHECK(F > 0 && F % 8 == 0, "F must be a positive multiple of 8");
+  int64_t N = x.numel() / F;
+  TORCH_CHECK(N < kFusedQuantMaxRows, "at most 2^21 rows");
+  check_bf16_vec(bias, "bias", F);
+  check_fp8_scale(scale);
+  auto q8 = x.options().dtype(at::kFloat8_e4m3fn);
+  auto amax = at::zeros({1}, x.options().dtype(at::kFloat));
+  auto q = at::empty({N, F}, q8);
+  auto qt = at::empty({F, N}, q8);
+  if (N == 0) return {q, qt, amax};
+  HIP_OK(launch_bias_gelu_fp8(x.const_data_ptr(), bias.const_data_ptr(),
+                              q.data_ptr(), qt.data_ptr(),
+                              (const float*)scale.const_data_ptr(),
+                              (float*)amax.data_ptr(), N, F, cur_stream()));
+  return {q, qt, amax};
+}
+
+// h = a (+ delta); LN(h) quantized to e4m3 in both layouts, no bf16 y:
+// (h, mean, rstd, q [N, H], qt [H, N], amax [1]), byte-equal to
+// add_layer_norm_fwd followed by fp8_quantize(y, scale, dual, e4m3)
+std::vector<at::Tensor> add_layer_norm_fp8(
+    const at::Tensor& a, const c10::optional<at::Tensor>& b,
+    const at::Tensor& w, const at::Tensor& bias, double eps,
+    const at::Tensor& scale) {
+  check_bf16_contig(a, "a");
+  TORCH_CHECK(a.dim() >= 1, "a must have a feature dimension");
+  int64_t H = a.size(-1);
+  TORCH_CHECK(H > 0 && H % 8 == 0, "H must be a positive multiple of 8");
+  // 16 rows of fp8 bytes are parked in 64 KB of LDS (FLN_MAX_H)
+  TORCH_CHECK(H <= 4096, "add_layer_norm_fp8 handles H <= 4096, got ", H);
+  int64_t N = a.numel() / H;
+  TORCH_CHECK(N < kFusedQuantMaxRows, "at most 2^21 rows");
+  if (b.has_value()) check_same_shape(*b, "b", a, "a");
+  check_bf16_vec(w, "w", H);
+  check_bf16_vec(bias, "bias", H);
+  check_fp8_scale(scale);
+  auto f32 = a.options().dtype(at::kFloat);
+  auto q8 = a.options().dtype(at::kFloat8_e4m3fn);
+  auto h = at::empty_like(a);
+  auto mean = at::empty({N}, f32);
+  auto rstd = at::empty({N}, f32);
+  auto amax = at::zeros({1}, f32);
+  auto q = at::empty({N, H}, q8);
+  auto qt = at::empty({H, N}, q8);
+  if (N == 0) return {h, mean, rstd, q, qt, amax};
+  const void* bp = b.has_value() ? b->const_data_ptr() : nullptr;
+  HIP_OK(launch_add_layer_norm_fp8(
+      a.const_data_ptr(), bp, w.const_data_ptr(), bias.const_data_ptr(),
+      h.mutable_data_ptr(), q.data_ptr(), qt.data_ptr(),
+      (float*)mean.mutable_data_ptr(), (float*)rstd.mutable_data_ptr(),
+      (const float*)scale.const_data_ptr(), (float*)amax.data_ptr(), N, H,
+      (float)eps, cur_stream()));
+  return {h, mean, rstd, q, qt, amax};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -804,7 +879,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // moe_combine_dw) added
   // 5: multi_tensor_sumsq_raw added; adamw_step_raw takes grad_sumsq and
   // max_grad_norm
-  m.attr("ABI_VERSION") = 5;
+  // 6: bias_gelu_fp8 and add_layer_norm_fp8 added
+  m.attr("ABI_VERSION") = 6;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)");
   m.def("add_layer_norm_fwd", &add_layer_norm_fwd,
@@ -825,6 +901,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "multi-tensor sum of squares (gfx950)");
   m.def("fp8_quantize", &fp8_quantize,
         "one-pass fp8 amax+cast, optional transposed twin (gfx950)");
+  m.def("bias_gelu_fp8", &bias_gelu_fp8,
+        "bias+GeLU forward emitting e4m3 q, qt and amax (gfx950)");
+  m.def("add_layer_norm_fp8", &add_layer_norm_fp8,
+        "residual-add + LayerNorm fwd emitting e4m3 q, qt and amax (gfx950)");
   m.def("cross_entropy_fwd", &cross_entropy_fwd, "fused CE fwd (gfx950)");
   m.def("cross_entropy_bwd", &cross_entropy_bwd, "fused CE bwd (gfx950)");
   m.def("attn_fwd", &attn_fwd, "flash attention fwd (gfx950 MFMA)",

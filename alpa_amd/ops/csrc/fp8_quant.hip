@@ -12,35 +12,8 @@
 // while the CURRENT amax is reduced into `amax_out` via atomicMax on
 // positive-float bits.
 #include "common.h"
+#include "fused_math.h"  // cvt2_fp8, atomic_max_f32, u8x8/u8x16
 #include "launchers.h"
-
-// e4m3: clamp 448; e5m2 (ISA name bf8): clamp 57344. RNE conversion via
-// the packed hardware converters.
-template <bool E5M2>
-__device__ __forceinline__ unsigned short cvt2_fp8(float a, float b) {
-  a = __builtin_amdgcn_fmed3f(a, E5M2 ? 57344.f : 448.f,
-                              E5M2 ? -57344.f : -448.f);
-  b = __builtin_amdgcn_fmed3f(b, E5M2 ? 57344.f : 448.f,
-                              E5M2 ? -57344.f : -448.f);
-  unsigned int packed =
-      E5M2 ? __builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false)
-           : __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  return (unsigned short)(packed & 0xffff);
-}
-
-__device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
-  // positive floats compare correctly as uints.  Guard with a plain
-  // read first: with ~80k blocks all reducing into ONE scalar, the
-  // serialized same-address atomics would otherwise dominate; after
-  // the first few blocks the running max is usually already >= v and
-  // the atomic is skipped (monotonic, so the race is benign).
-  volatile unsigned int* a = reinterpret_cast<volatile unsigned int*>(addr);
-  if (__float_as_uint(v) > *a)
-    atomicMax(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
-}
-
-typedef unsigned char u8x8 __attribute__((ext_vector_type(8)));
-typedef unsigned char u8x16 __attribute__((ext_vector_type(16)));
 
 // -------------------- single layout --------------------
 // src bf16 [total], q fp8 [total]; q = src / *scale; amax_out = max|src|

@@ -68,6 +68,18 @@ hipError_t launch_fp8_quantize_dual(const void* src, void* q, void* qt,
                                     int64_t M, int64_t N, int e5m2,
                                     hipStream_t stream);
 
+// ---- fp8_fused.hip ----
+// e4m3 only; amax must be zeroed by the caller, as for the quantize above
+hipError_t launch_bias_gelu_fp8(const void* x, const void* bias, void* q,
+                                void* qt, const float* scale, float* amax,
+                                int64_t M, int64_t F, hipStream_t stream);
+hipError_t launch_add_layer_norm_fp8(const void* a, const void* b,
+                                     const void* w, const void* bias, void* h,
+                                     void* q, void* qt, float* mean,
+                                     float* rstd, const float* scale,
+                                     float* amax, int64_t N, int64_t H,
+                                     float eps, hipStream_t stream);
+
 // ---- skinny_gemm.hip ----
 hipError_t launch_skinny_gemm(const void* wp, const void* x, float* part,
                               const void* bias_or_null, void* y,

@@ -103,6 +103,35 @@ def bias_gelu_bwd(dy: torch.Tensor, x: torch.Tensor, bias: torch.Tensor
     return dx.to(x.dtype), dbias
 
 
+def _fp8_dual(y: torch.Tensor, scale: torch.Tensor):
+    """Delayed-scale e4m3 cast of the rounded activation y [.., F]:
+    (q [N, F], qt [F, N], amax fp32 [1]) — what the dual quantize kernel
+    returns for y.reshape(-1, F)."""
+    y2 = y.reshape(-1, y.shape[-1])
+    q = (y2.float() / scale.float().reshape(())).clamp(-448.0, 448.0).to(
+        torch.float8_e4m3fn)
+    if y2.numel():
+        amax = y2.float().abs().amax().reshape(1)
+    else:
+        amax = torch.zeros(1, dtype=torch.float32, device=y.device)
+    return q, q.t().contiguous(), amax
+
+
+def bias_gelu_fp8(x: torch.Tensor, bias: torch.Tensor, scale: torch.Tensor):
+    """gelu(x + bias) rounded to x.dtype, then cast: (q, qt, amax)."""
+    return _fp8_dual(bias_gelu_fwd(x, bias), scale)
+
+
+def add_layer_norm_fp8(a: torch.Tensor, delta, weight: torch.Tensor,
+                       bias: torch.Tensor, eps: float, scale: torch.Tensor):
+    """h = a (+ delta); y = LN(h) rounded to a.dtype, then cast:
+    (h, mean, rstd, q, qt, amax)."""
+    h = a + delta if delta is not None else a.clone()
+    y, mean, rstd = layer_norm_fwd(h, weight, bias, eps)
+    q, qt, amax = _fp8_dual(y, scale)
+    return h, mean.reshape(-1), rstd.reshape(-1), q, qt, amax
+
+
 def _alibi_bias(alibi, Hh, S, Skv, device):
     """[1, Hh, S, Skv] ALiBi bias: slope_h * (kv_pos - q_pos); q global
     position is offset by Skv - S (cached decode)."""

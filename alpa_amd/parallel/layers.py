@@ -125,6 +125,24 @@ def _fp8_ok(x, weight, module=None) -> bool:
             weight.shape[0] % 16 == 0)
 
 
+def _fp8_fused_quant_ok(x, weight, module=None) -> bool:
+    """Gate for the producer-fused quantize (ops/fp8.py fp8_ln_linear /
+    fp8_gelu_linear): the flag, everything `_fp8_ok` asks of the consuming
+    linear, training (grad mode on), the fp8 weight-grad GEMM (with it off
+    the bf16 input is saved for dW, so it has to exist) and a bf16 input
+    for the HIP kernels.  x is the producer's INPUT: same rows and feature
+    count as the GEMM input it replaces."""
+    from ..global_env import global_config
+    if not (global_config.fp8_fused_quant and global_config.fp8_wgrad
+            and torch.is_grad_enabled()):
+        return False
+    return (_fp8_ok(x, weight, module) and x.dtype == torch.bfloat16
+            and ops.use_hip(x))
+
+
+_NO_DELTA = object()  # forward() sentinel: no LayerNorm in front
+
+
 class ColumnParallelLinear(nn.Module):
     """Y = X @ W^T + b with W row-sharded over out_features (each rank holds
     out_features/tp rows).  Output stays sharded along the feature dim.
@@ -160,9 +178,18 @@ class ColumnParallelLinear(nn.Module):
         else:
             self.register_parameter("bias", None)
 
-    def forward(self, x):
+    def forward(self, x, delta=_NO_DELTA, ln=None, defer_gelu=False):
+        """Single-arg: the linear (+ bias, + GeLU).  With (res, delta, ln):
+        the residual add and LayerNorm `ln` run in front and (h, y) comes
+        back, h = res + delta the residual stream (delta may be None).
+        `defer_gelu` (gelu layers only) returns the GEMM output before
+        bias and GeLU: the caller hands it to the next linear together
+        with this layer's bias (RowParallelLinear `gelu_bias`)."""
+        if delta is not _NO_DELTA:
+            return self._forward_ln(x, delta, ln, defer_gelu)
         x = copy_to_tp(x, self.mesh, self.axis)
         if ops.skinny_ok(x, self.weight, self):
+            assert not defer_gelu
             # decode-shaped inference (M <= 64): packed GEMV kernel
             if self.gelu:
                 return ops.bias_gelu(
@@ -172,13 +199,13 @@ class ColumnParallelLinear(nn.Module):
         if self._use_fp8(x):
             from ..ops.fp8 import fp8_linear
             if self.gelu:
-                return ops.bias_gelu(fp8_linear(x, self.weight,
-                                                module=self), self.bias)
+                pre = fp8_linear(x, self.weight, module=self)
+                return pre if defer_gelu else ops.bias_gelu(pre, self.bias)
             return fp8_linear(x, self.weight, self.bias, module=self)
         if self.gelu:
             assert self.bias is not None
-            return ops.bias_gelu(torch.matmul(x, self.weight.t()),
-                                 self.bias)
+            pre = torch.matmul(x, self.weight.t())
+            return pre if defer_gelu else ops.bias_gelu(pre, self.bias)
         if self.bias is not None:
             # bias fused into the hipBLASLt epilogue (addmm)
             return ops.linear_bias(x, self.weight, self.bias)
@@ -186,6 +213,23 @@ class ColumnParallelLinear(nn.Module):
 
     def _use_fp8(self, x):
         return _fp8_ok(x, self.weight, self)
+
+    def _forward_ln(self, res, delta, ln, defer_gelu):
+        tp1 = self.mesh is None or self.mesh.axis_size(self.axis) == 1
+        # tp > 1 puts copy_to_tp (all-reduce in backward) between the
+        # LayerNorm and this GEMM: the two stay separate ops there
+        # wider rows than the fused kernel's LDS tile holds stay unfused too
+        if tp1 and res.shape[-1] <= ops.ADD_LAYER_NORM_FP8_MAX_H and \
+                _fp8_fused_quant_ok(res, self.weight, self):
+            from ..ops.fp8 import fp8_ln_linear
+            h, y = fp8_ln_linear(res, delta, ln.weight, ln.bias, ln.eps,
+                                 self.weight,
+                                 None if self.gelu else self.bias, self)
+            if self.gelu and not defer_gelu:
+                y = ops.bias_gelu(y, self.bias)
+            return h, y
+        h, y = ops.add_layer_norm(res, delta, ln.weight, ln.bias, ln.eps)
+        return h, self.forward(y, defer_gelu=defer_gelu)
 
 
 class RowParallelLinear(nn.Module):
@@ -216,7 +260,21 @@ class RowParallelLinear(nn.Module):
         else:
             self.register_parameter("bias", None)
 
-    def forward(self, x):
+    def forward(self, x, gelu_bias=None):
+        """With `gelu_bias`, x is the previous linear's GEMM output before
+        its bias and GeLU (ColumnParallelLinear `defer_gelu`), which are
+        applied here: inside the fp8 quantize kernel when the fused route
+        is open, by ops.bias_gelu otherwise.  No collective sits between
+        the GeLU and this GEMM, so the join works at any tp."""
+        if gelu_bias is not None:
+            if _fp8_fused_quant_ok(x, self.weight, self):
+                from ..ops.fp8 import fp8_gelu_linear
+                y = fp8_gelu_linear(x, gelu_bias, self.weight, module=self)
+                y = reduce_from_tp(y, self.mesh, self.axis)
+                if self.bias is not None:
+                    y = ops.bias_add(y, self.bias)
+                return y
+            x = ops.bias_gelu(x, gelu_bias)
         if ops.skinny_ok(x, self.weight, self):
             y = ops.skinny_linear(x, self.weight, None, self)
         elif _fp8_ok(x, self.weight, self):

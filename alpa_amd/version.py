@@ -11,8 +11,9 @@ from __future__ import annotations
 
 __version__ = "0.1.0"
 
-#: minimum extension ABI this Python tree can drive
-MIN_HIP_OPS_ABI = 2
+#: minimum extension ABI this Python tree can drive (6: bias_gelu_fp8 and
+#: add_layer_norm_fp8, which the default fp8 training route calls)
+MIN_HIP_OPS_ABI = 6
 
 
 def check_hip_ops_version() -> int:
