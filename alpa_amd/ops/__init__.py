@@ -308,7 +308,8 @@ def flash_attention_varlen(q: torch.Tensor, k: torch.Tensor,
     """Decode attention with PER-BATCH KV lengths (continuous batching):
     slot b's queries attend to k[b, :, :kv_lens[b]].  Inference-only
     (no backward); the gfx950 kernel masks per element past each slot's
-    length."""
+    length and never loads k or v there, so a stale NaN or Inf in a cache
+    tail is harmless.  A slot of length 0 gives o = 0."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     lens = kv_lens.to(dtype=torch.int32)

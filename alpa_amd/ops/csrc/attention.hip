@@ -126,6 +126,10 @@ __global__ __launch_bounds__(ATTN_FWD_THREADS) void attn_fwd_kernel(
   const int my_skv = VL ? kv_lens[batch] : Skv;
   const float al_slope = AL ? alibi[bh % H] : 0.f;
   const int al_qoff = my_skv - S;
+  // rows at or past the slot's length are never loaded: their scores are
+  // masked, but P = 0 times a NaN or Inf left in V there would still be NaN
+  // (compile-time: without VL this is Skv, the original guard)
+  const int load_skv = VL ? min(my_skv, Skv) : Skv;
 
   // staging: load tile -> regs (two kv rows per thread so the V transpose
   // writes pair as b32)
@@ -142,7 +146,7 @@ __global__ __launch_bounds__(ATTN_FWD_THREADS) void attn_fwd_kernel(
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           int src = tile * ATTN_BLOCK_K + kvr + u;
-          if (src < Skv && dg + 8 <= D) {
+          if (src < load_skv && dg + 8 <= D) {
             kreg[2 * it + u] = *reinterpret_cast<const bf16x8*>(
                 kp + (int64_t)src * st.ks + dg);
             vreg[2 * it + u] = *reinterpret_cast<const bf16x8*>(

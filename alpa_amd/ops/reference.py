@@ -173,9 +173,11 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                                      device=q.device), diagonal=1)
         s = s.masked_fill(mask, float("-inf"))
     m = s.max(dim=-1, keepdim=True).values
-    p = torch.exp(s - m)
+    # a row with no visible key (kv_lens[b] == 0): o = 0, lse = -inf, as
+    # the kernel gives; every other row has l >= 1 and is unchanged
+    p = torch.exp(s - m.masked_fill(m == float("-inf"), 0.0))
     l = p.sum(dim=-1, keepdim=True)
-    o = torch.matmul(p / l, _up(v))
+    o = torch.matmul(p / l.masked_fill(l == 0, 1.0), _up(v))
     lse = (m + torch.log(l)).squeeze(-1)
     return o.to(q.dtype), lse
 
