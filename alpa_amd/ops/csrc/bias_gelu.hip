@@ -83,15 +83,6 @@ __global__ void bias_grad_partial_kernel(const short* __restrict__ dx,
   }
 }
 
-__global__ void bias_colsum_kernel(const float* __restrict__ part,
-                                   float* __restrict__ out, int P, int F) {
-  int col = blockIdx.x * blockDim.x + threadIdx.x;
-  if (col >= F) return;
-  float s = 0.f;
-  for (int p = 0; p < P; ++p) s += part[(int64_t)p * F + col];
-  out[col] = s;
-}
-
 extern "C" {
 
 hipError_t launch_bias_gelu_fwd(const void* x, const void* bias, void* y,
@@ -113,7 +104,7 @@ hipError_t launch_colsum_partial(const void* t, float* part, int64_t N,
 
 hipError_t launch_bias_gelu_bwd(const void* dy, const void* x,
                                 const void* bias, void* dx, float* db_part,
-                                float* db, int64_t N, int64_t F, int P,
+                                int64_t N, int64_t F, int P,
                                 hipStream_t stream) {
   int64_t total = N * F;
   int blocks = (int)min((int64_t)2048, ceil_div(total, 256 * 8));

@@ -57,18 +57,14 @@ void check_same_shape(const at::Tensor& t, const char* name,
               ref_name);
 }
 
-// Deterministic column-partial stripe count: enough (stripes x col-chunks)
-// blocks to fill 256 CUs, bounded by the row count.
-int stripes_for(int64_t N, int64_t cols) {
-  int64_t chunks = std::max<int64_t>(1, cols / 256);
-  int64_t p = std::max<int64_t>(64, 2048 / chunks);
-  return (int)std::min<int64_t>({p, N, 512});
-}
-
-// bias_gelu's dbias partial reads 8 cols/thread: fewer column chunks,
-// so more stripes keep >=2k blocks in flight
-int stripes_for_vec8(int64_t N, int64_t cols) {
-  int64_t chunks = std::max<int64_t>(1, cols / 2048);
+// Deterministic column-partial stripe count: enough (stripes x column
+// chunks) blocks to fill 256 CUs, bounded by the row count.  `chunk_cols` is
+// a tuning constant per kernel, not its block width: 256 for the LayerNorm
+// dw/db partial (whose blocks cover 1024 columns), 2048 for the bias-grad
+// partial, which has fewer column blocks and so wants more stripes.  The
+// result fixes the summation order of dw, db and dbias.
+int stripes_for(int64_t N, int64_t cols, int64_t chunk_cols) {
+  int64_t chunks = std::max<int64_t>(1, cols / chunk_cols);
   int64_t p = std::max<int64_t>(64, 2048 / chunks);
   return (int)std::min<int64_t>({p, N, 512});
 }
@@ -107,7 +103,7 @@ std::pair<at::Tensor, at::Tensor> layer_norm_dwdb(const at::Tensor& dy,
   auto f32 = x.options().dtype(at::kFloat);
   auto dw = at::empty({H}, f32);
   auto db = at::empty({H}, f32);
-  const int kStripes = stripes_for(N, H);
+  const int kStripes = stripes_for(N, H, 256);
   auto dw_part = at::empty({kStripes, H}, f32);
   auto db_part = at::empty({kStripes, H}, f32);
   HIP_OK(launch_layer_norm_bwd_dwdb(
@@ -115,8 +111,7 @@ std::pair<at::Tensor, at::Tensor> layer_norm_dwdb(const at::Tensor& dy,
       (const float*)mean.const_data_ptr(),
       (const float*)rstd.const_data_ptr(),
       (float*)dw_part.mutable_data_ptr(), (float*)db_part.mutable_data_ptr(),
-      (float*)dw.mutable_data_ptr(), (float*)db.mutable_data_ptr(), N, H,
-      kStripes, cur_stream()));
+      N, H, kStripes, cur_stream()));
   at::sum_out(dw, dw_part, {0});
   at::sum_out(db, db_part, {0});
   return {dw, db};
@@ -137,7 +132,7 @@ std::vector<at::Tensor> layer_norm_bwd(const at::Tensor& dy,
   check_row_stats(rstd, "rstd", N);
   auto dx = at::empty_like(x);
   HIP_OK(launch_layer_norm_bwd_dx(
-      dy.const_data_ptr(), x.const_data_ptr(), w.const_data_ptr(),
+      dy.const_data_ptr(), nullptr, x.const_data_ptr(), w.const_data_ptr(),
       (const float*)mean.const_data_ptr(), (const float*)rstd.const_data_ptr(),
       dx.mutable_data_ptr(), N, H, cur_stream()));
   auto [dw, db] = layer_norm_dwdb(dy, x, mean, rstd, N, H);
@@ -187,7 +182,7 @@ std::vector<at::Tensor> add_layer_norm_bwd(
   check_row_stats(rstd, "rstd", N);
   auto dx = at::empty_like(h);
   const void* dhp = dh.has_value() ? dh->const_data_ptr() : nullptr;
-  HIP_OK(launch_add_layer_norm_bwd_dx(
+  HIP_OK(launch_layer_norm_bwd_dx(
       dy.const_data_ptr(), dhp, h.const_data_ptr(), w.const_data_ptr(),
       (const float*)mean.const_data_ptr(),
       (const float*)rstd.const_data_ptr(), dx.mutable_data_ptr(), N, H,
@@ -221,14 +216,13 @@ std::vector<at::Tensor> bias_gelu_bwd(const at::Tensor& dy,
   check_bf16_vec(bias, "bias", F);
   auto dx = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
-  const int kStripes = stripes_for_vec8(N, F);
+  const int kStripes = stripes_for(N, F, 2048);
   auto db = at::empty({F}, f32);
   auto db_part = at::empty({kStripes, F}, f32);
   HIP_OK(launch_bias_gelu_bwd(dy.const_data_ptr(), x.const_data_ptr(),
                               bias.const_data_ptr(), dx.mutable_data_ptr(),
-                              (float*)db_part.mutable_data_ptr(),
-                              (float*)db.mutable_data_ptr(), N, F, kStripes,
-                              cur_stream()));
+                              (float*)db_part.mutable_data_ptr(), N, F,
+                              kStripes, cur_stream()));
   at::sum_out(db, db_part, {0});
   return {dx, db};
 }
@@ -241,7 +235,7 @@ at::Tensor colsum_bf16(const at::Tensor& t) {
   int64_t F = t.size(-1);
   int64_t N = t.numel() / F;
   auto f32 = t.options().dtype(at::kFloat);
-  const int kStripes = stripes_for_vec8(N, F);
+  const int kStripes = stripes_for(N, F, 2048);
   auto part = at::empty({kStripes, F}, f32);
   auto out = at::empty({F}, f32);
   HIP_OK(launch_colsum_partial(t.const_data_ptr(),

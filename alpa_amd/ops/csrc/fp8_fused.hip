@@ -16,15 +16,14 @@
 #include "common.h"
 #include "fused_math.h"
 #include "launchers.h"
+#include "layernorm_rows.h"
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------ bias + GeLU
 // x [M, F] bf16, bias [F] -> q e4m3 [M, F], qt e4m3 [F, M]; no bf16 output.
-// The tiling of fp8_quantize_dual_kernel: a 64x64 tile converted into LDS
-// as fp8 bytes, then drained row-major and transposed, 16 B per lane.
-#define FQT 64
-
+// The tile routine of fp8_quantize_dual_kernel (fused_math.h) with a loader
+// that computes the bf16 rounding of gelu(x + bias) instead of reading it.
 __global__ void bias_gelu_fp8_kernel(const short* __restrict__ x,
                                      const short* __restrict__ bias,
                                      unsigned char* __restrict__ q,
@@ -32,116 +31,41 @@ __global__ void bias_gelu_fp8_kernel(const short* __restrict__ x,
                                      const float* __restrict__ scale,
                                      float* __restrict__ amax_out,
                                      int64_t M, int64_t F) {
-  const float inv = 1.0f / fmaxf(*scale, 1e-12f);
-  __shared__ unsigned char tile[FQT][FQT + 4];  // +4 bytes: depivot banks
-  const int64_t row0 = (int64_t)blockIdx.y * FQT;
-  const int64_t col0 = (int64_t)blockIdx.x * FQT;
-  const int t = threadIdx.x;           // 256 threads
-  const int tc = (t & 15) * 4;         // 4 consecutive cols
-  const int tr = t >> 4;               // 16 rows per pass
-  const bool interior = (row0 + FQT <= M) && (col0 + FQT <= F);
-  // 16-byte stores need 16-byte row pitches (F % 8 == 0 alone gives 8)
-  const bool vec_q = interior && (F % 16 == 0);
-  const bool vec_qt = interior && (M % 16 == 0);
-  // F % 8 == 0 and tc % 4 == 0: a column quad is inside or outside whole
-  const bool col_ok = col0 + tc < F;
-  bf16x4 bv = {0, 0, 0, 0};
-  if (col_ok) bv = *reinterpret_cast<const bf16x4*>(bias + col0 + tc);
-  float amax = 0.f;
+  fp8_quantize_tile<false>(
+      [&](int64_t gr, int64_t gc) {
+        f32x4 f = {0.f, 0.f, 0.f, 0.f};
+        // F % 8 == 0 and gc % 4 == 0: a column quad is inside or outside whole
+        if (gr < M && gc < F) {
+          bf16x4 v = *reinterpret_cast<const bf16x4*>(x + gr * F + gc);
+          // re-loaded for each of a thread's four rows, on purpose: the
+          // quad stays in L1, and the loader stays a function of (row, col)
+          bf16x4 bv = *reinterpret_cast<const bf16x4*>(bias + gc);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = tr + i * 16;
-    const int64_t gr = row0 + r;
-    // outside the tensor: zeros, which neither move amax nor get stored
-    float f[4] = {0.f, 0.f, 0.f, 0.f};
-    if (gr < M && col_ok) {
-      bf16x4 v = *reinterpret_cast<const bf16x4*>(x + gr * F + col0 + tc);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        f[j] = bf2f(f2bf(gelu_f(bf2f(v[j]) + bf2f(bv[j]))));
-    }
-    unsigned char b[4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      unsigned short p = cvt2_fp8<false>(f[2 * j] * inv, f[2 * j + 1] * inv);
-      b[2 * j] = (unsigned char)(p & 0xff);
-      b[2 * j + 1] = (unsigned char)(p >> 8);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      amax = fmaxf(amax, fabsf(f[j]));
-      tile[r][tc + j] = b[j];
-    }
-  }
-  __syncthreads();
-  // row-major q, 16 B/lane (4 lanes cover one 64-B tile row)
-  {
-    const int r = t >> 2;               // 0..63 tile row
-    const int c16 = (t & 3) * 16;
-    const int64_t gr = row0 + r;
-    if (vec_q) {
-      u8x16 v;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = tile[r][c16 + j];
-      *reinterpret_cast<u8x16*>(q + gr * F + col0 + c16) = v;
-    } else if (gr < M) {
-      for (int j = 0; j < 16; ++j)
-        if (col0 + c16 + j < F) q[gr * F + col0 + c16 + j] = tile[r][c16 + j];
-    }
-  }
-  // transposed qt, 16 B/lane along the original row dim
-  {
-    const int r = t >> 2;               // 0..63 = original col = qt row
-    const int c16 = (t & 3) * 16;       // original rows = qt cols
-    const int64_t gq = col0 + r;
-    if (vec_qt) {
-      u8x16 v;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = tile[c16 + j][r];
-      *reinterpret_cast<u8x16*>(qt + gq * M + row0 + c16) = v;
-    } else if (gq < F) {
-      for (int j = 0; j < 16; ++j)
-        if (row0 + c16 + j < M)
-          qt[gq * M + row0 + c16 + j] = tile[c16 + j][r];
-    }
-  }
-  __shared__ float red[16];
-  amax = block_reduce_max(amax, red);
-  if (threadIdx.x == 0) atomic_max_f32(amax_out, amax);
+          for (int j = 0; j < 4; ++j)
+            f[j] = bf2f(f2bf(gelu_f(bf2f(v[j]) + bf2f(bv[j]))));
+        }
+        return f;
+      },
+      q, qt, scale, amax_out, M, F);
 }
 
 // ------------------------------------------------------- add + LayerNorm
 // h = a + b (b may be null); y = LN(h) * w + bias is quantized, not stored.
 //
-// A workgroup walks FLN_ROWS consecutive rows, FLN_RI at a time, each with
-// the row loop of add_layer_norm_fwd_kernel (h written, the two block
-// reductions in the same order, statistics of the rounded h).  The
-// normalize pass rounds y to bf16, casts it, stores q and parks the bytes
-// in an LDS tile [16][H]; at the end the tile is drained into qt, 16 B
-// along the row dimension per store.  16 * H bytes of LDS: H <= 4096.
+// A workgroup walks FLN_ROWS consecutive rows, FLN_RI at a time, through
+// layer_norm_rows, the row passes add_layer_norm_fwd_kernel runs: h, mean,
+// rstd and the bf16 rounding of y are that kernel's by construction.  The
+// epilogue casts the rounded y, stores q and parks the bytes in an LDS tile
+// [16][H]; at the end the tile is drained into qt, 16 B along the row
+// dimension per store.  16 * H bytes of LDS: H <= 4096.
 // Consecutive row groups run on one XCD (xcd_swizzle), so the 16-B pieces
 // of a qt line meet in one L2.
-#define FLN_BLOCK 256
+#define FLN_BLOCK LN_BLOCK
 #define FLN_ROWS 16
 #define FLN_RI 4
 #define FLN_MAX_H 4096
 
-// The compiler builds add_layer_norm_fwd_kernel's variance from separate
-// multiplies and adds and its normalize step from fused multiply-adds.  A
-// kernel that walks several rows at once is vectorized differently and
-// would contract differently if left to the compiler, so both choices are
-// spelled out here; the byte comparisons in the GPU tests hold them to
-// what the one-row kernel does.
-__device__ __forceinline__ float fln_sq_acc(float s, float d) {
-#pragma clang fp contract(off)
-  float p = d * d;
-  return s + p;
-}
-
-// RI rows go through the three passes of add_layer_norm_fwd_kernel side by
-// side: the loads of all RI rows are in flight together, each row keeps its
-// own partial sums and its own block reductions, so every row's arithmetic
-// is that of the one-row kernel.
+// RI rows from `row` on: q goes out, the bytes are parked in tile_rows
 template <int RI>
 __device__ __forceinline__ void fln_rows(
     const short* __restrict__ a, const short* __restrict__ b,
@@ -150,91 +74,17 @@ __device__ __forceinline__ void fln_rows(
     float* __restrict__ mean_out, float* __restrict__ rstd_out,
     unsigned char* tile_rows, float* red, int64_t row, int H, float eps,
     float inv, float& amax) {
-  const short* ar = a + row * H;
-  const short* br = (b == nullptr) ? nullptr : b + row * H;
-  short* hr = h + row * H;
-  float s[RI], mean[RI], rstd[RI];
+  layer_norm_rows<RI, true>(
+      a, b, w, bias, h, mean_out, rstd_out, red, row, H, eps,
+      [&](int u, int i, bf16x8 y) {
+        float f[8];
 #pragma unroll
-  for (int u = 0; u < RI; ++u) s[u] = 0.f;
-  for (int i = threadIdx.x * 8; i < H; i += FLN_BLOCK * 8) {
-    bf16x8 av[RI], bv[RI];
-#pragma unroll
-    for (int u = 0; u < RI; ++u) {
-      av[u] = *reinterpret_cast<const bf16x8*>(ar + (int64_t)u * H + i);
-      if (br != nullptr)
-        bv[u] = *reinterpret_cast<const bf16x8*>(br + (int64_t)u * H + i);
-    }
-#pragma unroll
-    for (int u = 0; u < RI; ++u) {
-      bf16x8 hv;
-      if (br != nullptr) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          hv[j] = f2bf(bf2f(av[u][j]) + bf2f(bv[u][j]));
-          s[u] += bf2f(hv[j]);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          hv[j] = av[u][j];
-          s[u] += bf2f(av[u][j]);
-        }
-      }
-      *reinterpret_cast<bf16x8*>(hr + (int64_t)u * H + i) = hv;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < RI; ++u) mean[u] = block_reduce_sum(s[u], red) / H;
-  // two-pass variance; each thread re-reads the h elements it wrote itself
-  // (here and in the normalize pass), so no fence is needed
-#pragma unroll
-  for (int u = 0; u < RI; ++u) s[u] = 0.f;
-  for (int i = threadIdx.x * 8; i < H; i += FLN_BLOCK * 8) {
-#pragma unroll
-    for (int u = 0; u < RI; ++u) {
-      bf16x8 hv = *reinterpret_cast<const bf16x8*>(hr + (int64_t)u * H + i);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float d = bf2f(hv[j]) - mean[u];
-        s[u] = fln_sq_acc(s[u], d);
-      }
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < RI; ++u)
-    rstd[u] = rsqrtf(block_reduce_sum(s[u], red) / H + eps);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int u = 0; u < RI; ++u) {
-      mean_out[row + u] = mean[u];
-      rstd_out[row + u] = rstd[u];
-    }
-  }
-  // normalize, round to bf16, cast; q goes out, the bytes are parked
-  for (int i = threadIdx.x * 8; i < H; i += FLN_BLOCK * 8) {
-    const bf16x8 wv = *reinterpret_cast<const bf16x8*>(w + i);
-    const bf16x8 bv2 = *reinterpret_cast<const bf16x8*>(bias + i);
-#pragma unroll
-    for (int u = 0; u < RI; ++u) {
-      bf16x8 hv = *reinterpret_cast<const bf16x8*>(hr + (int64_t)u * H + i);
-      float f[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float xhat = (bf2f(hv[j]) - mean[u]) * rstd[u];
-        f[j] = bf2f(f2bf(__builtin_fmaf(xhat, bf2f(wv[j]), bf2f(bv2[j]))));
-        amax = fmaxf(amax, fabsf(f[j]));
-      }
-      u8x8 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        unsigned short p = cvt2_fp8<false>(f[2 * j] * inv, f[2 * j + 1] * inv);
-        o[2 * j] = (unsigned char)(p & 0xff);
-        o[2 * j + 1] = (unsigned char)(p >> 8);
-      }
-      *reinterpret_cast<u8x8*>(q + (row + u) * H + i) = o;
-      *reinterpret_cast<u8x8*>(tile_rows + (int64_t)u * H + i) = o;
-    }
-  }
+        for (int j = 0; j < 8; ++j) f[j] = bf2f(y[j]);
+        u8x8 o;
+        fp8_pack<false, 4>(f, inv, amax, o);
+        *reinterpret_cast<u8x8*>(q + (row + u) * H + i) = o;
+        *reinterpret_cast<u8x8*>(tile_rows + (int64_t)u * H + i) = o;
+      });
 }
 
 template <int RI>
@@ -257,7 +107,7 @@ add_layer_norm_fp8_kernel(const short* __restrict__ a,
   // barrier) before that group parks its bytes, and row 15 parks last.
   extern __shared__ __attribute__((aligned(16))) unsigned char tile[];
   float* red = reinterpret_cast<float*>(tile + (FLN_ROWS - 1) * H);
-  const float inv = 1.0f / fmaxf(*scale, 1e-12f);
+  const float inv = fp8_inv_scale(scale);
   const int64_t row0 =
       (int64_t)xcd_swizzle((int)blockIdx.x, (int)gridDim.x) * FLN_ROWS;
   const int nrows = (int)min((int64_t)FLN_ROWS, N - row0);
@@ -306,7 +156,7 @@ extern "C" {
 hipError_t launch_bias_gelu_fp8(const void* x, const void* bias, void* q,
                                 void* qt, const float* scale, float* amax,
                                 int64_t M, int64_t F, hipStream_t stream) {
-  dim3 grid((uint32_t)ceil_div(F, FQT), (uint32_t)ceil_div(M, FQT));
+  dim3 grid((uint32_t)ceil_div(F, FP8_TILE), (uint32_t)ceil_div(M, FP8_TILE));
   bias_gelu_fp8_kernel<<<grid, dim3(256), 0, stream>>>(
       (const short*)x, (const short*)bias, (unsigned char*)q,
       (unsigned char*)qt, scale, amax, M, F);

@@ -16,32 +16,30 @@ extern "C" {
 hipError_t launch_layer_norm_fwd(const void* x, const void* w, const void* b,
                                  void* y, float* mean, float* rstd, int64_t N,
                                  int64_t H, float eps, hipStream_t stream);
-hipError_t launch_layer_norm_bwd_dx(const void* dy, const void* x,
-                                    const void* w, const float* mean,
-                                    const float* rstd, void* dx, int64_t N,
-                                    int64_t H, hipStream_t stream);
+// dh: residual gradient added to dx, or null
+hipError_t launch_layer_norm_bwd_dx(const void* dy, const void* dh,
+                                    const void* x, const void* w,
+                                    const float* mean, const float* rstd,
+                                    void* dx, int64_t N, int64_t H,
+                                    hipStream_t stream);
+// dw_part/db_part [P, H]: the caller sums them over P
 hipError_t launch_layer_norm_bwd_dwdb(const void* dy, const void* x,
                                       const float* mean, const float* rstd,
                                       float* dw_part, float* db_part,
-                                      float* dw, float* db, int64_t N,
-                                      int64_t H, int P, hipStream_t stream);
+                                      int64_t N, int64_t H, int P,
+                                      hipStream_t stream);
 hipError_t launch_add_layer_norm_fwd(const void* a, const void* b,
                                      const void* w, const void* bias,
                                      void* h, void* y, float* mean,
                                      float* rstd, int64_t N, int64_t H,
                                      float eps, hipStream_t stream);
-hipError_t launch_add_layer_norm_bwd_dx(const void* dy, const void* dh,
-                                        const void* x, const void* w,
-                                        const float* mean, const float* rstd,
-                                        void* dx, int64_t N, int64_t H,
-                                        hipStream_t stream);
 
 // ---- bias_gelu.hip ----
 hipError_t launch_bias_gelu_fwd(const void* x, const void* bias, void* y,
                                 int64_t N, int64_t F, hipStream_t stream);
 hipError_t launch_bias_gelu_bwd(const void* dy, const void* x,
                                 const void* bias, void* dx, float* db_part,
-                                float* db, int64_t N, int64_t F, int P,
+                                int64_t N, int64_t F, int P,
                                 hipStream_t stream);
 hipError_t launch_colsum_partial(const void* t, float* part, int64_t N,
                                  int64_t F, int P, hipStream_t stream);

@@ -9,11 +9,11 @@
 // kernel table: "LayerNorm fwd/bwd | elementwise+reduce fusion | [B·S, H]").
 #include "common.h"
 #include "launchers.h"
-
-#define LN_BLOCK 256
+#include "layernorm_rows.h"
 
 // ---------------------------------------------------------------- forward
-// x [N, H] bf16, w/b [H] bf16 -> y [N, H] bf16, mean/rstd [N] fp32
+// x [N, H] bf16, w/b [H] bf16 -> y [N, H] bf16, mean/rstd [N] fp32.
+// One workgroup per row; the passes are layer_norm_rows (layernorm_rows.h).
 __global__ void layer_norm_fwd_kernel(const short* __restrict__ x,
                                       const short* __restrict__ w,
                                       const short* __restrict__ b,
@@ -21,68 +21,55 @@ __global__ void layer_norm_fwd_kernel(const short* __restrict__ x,
                                       float* __restrict__ mean_out,
                                       float* __restrict__ rstd_out,
                                       int H, float eps) {
-  const int row = blockIdx.x;
-  const short* xr = x + (int64_t)row * H;
-  short* yr = y + (int64_t)row * H;
   __shared__ float red[LN_BLOCK / 64];
+  const int row = blockIdx.x;
+  short* yr = y + (int64_t)row * H;
+  layer_norm_rows<1, false>(
+      x, nullptr, w, b, nullptr, mean_out, rstd_out, red, row, H, eps,
+      [&](int, int i, bf16x8 o) { *reinterpret_cast<bf16x8*>(yr + i) = o; });
+}
 
-  // pass 1: mean (vectorized)
-  float s = 0.f;
-  for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
-    bf16x8 v = *reinterpret_cast<const bf16x8*>(xr + i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += bf2f(v[j]);
-  }
-  const float mean = block_reduce_sum(s, red) / H;
-  // pass 2: variance as the mean of squared deviations.  The one-pass
-  // E[x^2] - mean^2 form cancels catastrophically once |mean| >> std
-  // (a near-constant row came out with a negative variance, so NaN).
-  // The row was just read, so this pass hits L2.
-  float ss = 0.f;
-  for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
-    bf16x8 v = *reinterpret_cast<const bf16x8*>(xr + i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float d = bf2f(v[j]) - mean;
-      ss += d * d;
-    }
-  }
-  const float rstd = rsqrtf(block_reduce_sum(ss, red) / H + eps);
-  if (threadIdx.x == 0) {
-    mean_out[row] = mean;
-    rstd_out[row] = rstd;
-  }
-
-  // pass 3: normalize (x re-read hits L2/L3)
-  for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
-    bf16x8 v = *reinterpret_cast<const bf16x8*>(xr + i);
-    bf16x8 wv = *reinterpret_cast<const bf16x8*>(w + i);
-    bf16x8 bv = *reinterpret_cast<const bf16x8*>(b + i);
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float xhat = (bf2f(v[j]) - mean) * rstd;
-      o[j] = f2bf(xhat * bf2f(wv[j]) + bf2f(bv[j]));
-    }
-    *reinterpret_cast<bf16x8*>(yr + i) = o;
-  }
+// Fused residual-add + LayerNorm: h = a + b; y = LN(h) * w + bias.
+// Saves the separate elementwise-add pass over the residual stream
+// (the reference gets this from XLA fusion).  b may be null (plain LN
+// with h written = a, used at the embedding boundary).
+__global__ void add_layer_norm_fwd_kernel(const short* __restrict__ a,
+                                          const short* __restrict__ b,
+                                          const short* __restrict__ w,
+                                          const short* __restrict__ bias,
+                                          short* __restrict__ h,
+                                          short* __restrict__ y,
+                                          float* __restrict__ mean_out,
+                                          float* __restrict__ rstd_out,
+                                          int H, float eps) {
+  __shared__ float red[LN_BLOCK / 64];
+  const int row = blockIdx.x;
+  short* yr = y + (int64_t)row * H;
+  layer_norm_rows<1, true>(
+      a, b, w, bias, h, mean_out, rstd_out, red, row, H, eps,
+      [&](int, int i, bf16x8 o) { *reinterpret_cast<bf16x8*>(yr + i) = o; });
 }
 
 // ---------------------------------------------------------------- backward dx
-// dx = (wdy - mean(wdy) - xhat * mean(wdy*xhat)) * rstd
-__global__ void layer_norm_bwd_dx_kernel(const short* __restrict__ dy,
-                                         const short* __restrict__ x,
-                                         const short* __restrict__ w,
-                                         const float* __restrict__ mean_in,
-                                         const float* __restrict__ rstd_in,
-                                         short* __restrict__ dx, int H) {
+// dx = (wdy - mean(wdy) - xhat * mean(wdy*xhat)) * rstd, plus the residual
+// gradient dh when HAS_DH (add_layer_norm_bwd with a dh).
+template <bool HAS_DH>
+__global__ void layer_norm_bwd_dx_kernel(
+    const short* __restrict__ dy, const short* __restrict__ dh,
+    const short* __restrict__ x, const short* __restrict__ w,
+    const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+    short* __restrict__ dx, int H) {
   const int row = blockIdx.x;
   const short* dyr = dy + (int64_t)row * H;
+  const short* dhr = HAS_DH ? dh + (int64_t)row * H : nullptr;
   const short* xr = x + (int64_t)row * H;
   short* dxr = dx + (int64_t)row * H;
   const float mean = mean_in[row], rstd = rstd_in[row];
   __shared__ float red[LN_BLOCK / 64];
 
+  // two passes over the row (L2-resident for these row sizes; a
+  // register-cached single-read variant measured NEUTRAL-to-worse —
+  // the extra VGPRs bought nothing).
   float c1 = 0.f, c2 = 0.f;
   for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
     bf16x8 dv = *reinterpret_cast<const bf16x8*>(dyr + i);
@@ -103,22 +90,27 @@ __global__ void layer_norm_bwd_dx_kernel(const short* __restrict__ dy,
     bf16x8 dv = *reinterpret_cast<const bf16x8*>(dyr + i);
     bf16x8 xv = *reinterpret_cast<const bf16x8*>(xr + i);
     bf16x8 wv = *reinterpret_cast<const bf16x8*>(w + i);
+    bf16x8 hv;
+    if (HAS_DH) hv = *reinterpret_cast<const bf16x8*>(dhr + i);
     bf16x8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float wdy = bf2f(dv[j]) * bf2f(wv[j]);
       float xhat = (bf2f(xv[j]) - mean) * rstd;
-      o[j] = f2bf((wdy - c1 - xhat * c2) * rstd);
+      float g = (wdy - c1 - xhat * c2) * rstd;
+      if (HAS_DH) g += bf2f(hv[j]);
+      o[j] = f2bf(g);
     }
     *reinterpret_cast<bf16x8*>(dxr + i) = o;
   }
 }
 
 // ------------------------------------------------------------- backward dw/db
-// Striped partials: grid (H/CHUNK, P); block (r, p) accumulates rows
-// r*? — rows p, p+P, p+2P... over column chunk. Output partial [P, H] fp32;
-// final sum over P done by a tiny second kernel.
-#define LNB_COLS 256  // columns per block (1 per thread)
+// Striped partials: grid (ceil(H / 1024), P); block (c, p) sums stripe p, a
+// contiguous range of rows, over its 1024 columns.  Output partial [P, H]
+// fp32; the caller sums over P (at::sum — its parallel reduce beats a serial
+// per-column loop).
+#define LNB_COLS 256  // threads per block, 4 columns each
 
 __global__ void layer_norm_bwd_dwdb_partial(const short* __restrict__ dy,
                                             const short* __restrict__ x,
@@ -167,15 +159,6 @@ __global__ void layer_norm_bwd_dwdb_partial(const short* __restrict__ dy,
   }
 }
 
-__global__ void column_sum_kernel(const float* __restrict__ part,
-                                  float* __restrict__ out, int P, int H) {
-  int col = blockIdx.x * blockDim.x + threadIdx.x;
-  if (col >= H) return;
-  float s = 0.f;
-  for (int p = 0; p < P; ++p) s += part[(int64_t)p * H + col];
-  out[col] = s;
-}
-
 // ---------------------------------------------------------------- launchers
 extern "C" {
 
@@ -188,162 +171,30 @@ hipError_t launch_layer_norm_fwd(const void* x, const void* w, const void* b,
   return hipGetLastError();
 }
 
-hipError_t launch_layer_norm_bwd_dx(const void* dy, const void* x,
-                                    const void* w, const float* mean,
-                                    const float* rstd, void* dx, int64_t N,
-                                    int64_t H, hipStream_t stream) {
-  layer_norm_bwd_dx_kernel<<<dim3((uint32_t)N), dim3(LN_BLOCK), 0, stream>>>(
-      (const short*)dy, (const short*)x, (const short*)w, mean, rstd,
-      (short*)dx, (int)H);
+hipError_t launch_layer_norm_bwd_dx(const void* dy, const void* dh,
+                                    const void* x, const void* w,
+                                    const float* mean, const float* rstd,
+                                    void* dx, int64_t N, int64_t H,
+                                    hipStream_t stream) {
+  auto kernel = dh != nullptr ? layer_norm_bwd_dx_kernel<true>
+                              : layer_norm_bwd_dx_kernel<false>;
+  kernel<<<dim3((uint32_t)N), dim3(LN_BLOCK), 0, stream>>>(
+      (const short*)dy, (const short*)dh, (const short*)x, (const short*)w,
+      mean, rstd, (short*)dx, (int)H);
   return hipGetLastError();
 }
 
 hipError_t launch_layer_norm_bwd_dwdb(const void* dy, const void* x,
                                       const float* mean, const float* rstd,
                                       float* dw_part, float* db_part,
-                                      float* /*dw*/, float* /*db*/, int64_t N,
-                                      int64_t H, int P, hipStream_t stream) {
+                                      int64_t N, int64_t H, int P,
+                                      hipStream_t stream) {
   dim3 grid((uint32_t)ceil_div(H, LNB_COLS * 4), P);
   layer_norm_bwd_dwdb_partial<<<grid, dim3(LNB_COLS), 0, stream>>>(
       (const short*)dy, (const short*)x, mean, rstd, dw_part, db_part,
       (int)N, (int)H);
-  // final P-row reduction handled by the caller (at::sum — parallel
-  // reduce kernel beats the serial per-column loop)
   return hipGetLastError();
 }
-
-}  // extern "C"
-
-// ------------------------------------------------------------------
-// Fused residual-add + LayerNorm: h = a + b; y = LN(h) * w + bias.
-// Saves the separate elementwise-add pass over the residual stream
-// (the reference gets this from XLA fusion).  b may be null (plain LN
-// with h written = a, used at the embedding boundary).
-__global__ void add_layer_norm_fwd_kernel(const short* __restrict__ a,
-                                          const short* __restrict__ b,
-                                          const short* __restrict__ w,
-                                          const short* __restrict__ bias,
-                                          short* __restrict__ h,
-                                          short* __restrict__ y,
-                                          float* __restrict__ mean_out,
-                                          float* __restrict__ rstd_out,
-                                          int H, float eps) {
-  const int row = blockIdx.x;
-  const short* ar = a + (int64_t)row * H;
-  const short* br = (b == nullptr) ? nullptr : b + (int64_t)row * H;
-  short* hr = h + (int64_t)row * H;
-  short* yr = y + (int64_t)row * H;
-  __shared__ float red[LN_BLOCK / 64];
-
-  // statistics are those of the ROUNDED h: that is the tensor the
-  // normalize pass, the backward and every later layer see
-  float s = 0.f;
-  for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
-    bf16x8 av = *reinterpret_cast<const bf16x8*>(ar + i);
-    bf16x8 hv;
-    if (br != nullptr) {
-      bf16x8 bv = *reinterpret_cast<const bf16x8*>(br + i);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        hv[j] = f2bf(bf2f(av[j]) + bf2f(bv[j]));
-        s += bf2f(hv[j]);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        hv[j] = av[j];
-        s += bf2f(av[j]);
-      }
-    }
-    *reinterpret_cast<bf16x8*>(hr + i) = hv;
-  }
-  const float mean = block_reduce_sum(s, red) / H;
-  // two-pass variance (see layer_norm_fwd_kernel); each thread re-reads
-  // the h elements it wrote itself, so no fence is needed
-  float ss = 0.f;
-  for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
-    bf16x8 hv = *reinterpret_cast<const bf16x8*>(hr + i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float d = bf2f(hv[j]) - mean;
-      ss += d * d;
-    }
-  }
-  const float rstd = rsqrtf(block_reduce_sum(ss, red) / H + eps);
-  if (threadIdx.x == 0) {
-    mean_out[row] = mean;
-    rstd_out[row] = rstd;
-  }
-  for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
-    bf16x8 hv = *reinterpret_cast<const bf16x8*>(hr + i);
-    bf16x8 wv = *reinterpret_cast<const bf16x8*>(w + i);
-    bf16x8 bv2 = *reinterpret_cast<const bf16x8*>(bias + i);
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float xhat = (bf2f(hv[j]) - mean) * rstd;
-      o[j] = f2bf(xhat * bf2f(wv[j]) + bf2f(bv2[j]));
-    }
-    *reinterpret_cast<bf16x8*>(yr + i) = o;
-  }
-}
-
-// backward dx with an extra residual-gradient term:
-// g = LN_bwd_dx(dy) + dh   (dh may be null)
-__global__ void add_layer_norm_bwd_dx_kernel(
-    const short* __restrict__ dy, const short* __restrict__ dh,
-    const short* __restrict__ x, const short* __restrict__ w,
-    const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
-    short* __restrict__ dx, int H) {
-  const int row = blockIdx.x;
-  const short* dyr = dy + (int64_t)row * H;
-  const short* dhr = (dh == nullptr) ? nullptr : dh + (int64_t)row * H;
-  const short* xr = x + (int64_t)row * H;
-  short* dxr = dx + (int64_t)row * H;
-  const float mean = mean_in[row], rstd = rstd_in[row];
-  __shared__ float red[LN_BLOCK / 64];
-
-  // two passes over the row (L2-resident for these row sizes; a
-  // register-cached single-read variant measured NEUTRAL-to-worse —
-  // the extra VGPRs bought nothing).  dh (residual grad) read is
-  // vectorized.
-  float c1 = 0.f, c2 = 0.f;
-  for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
-    bf16x8 dv = *reinterpret_cast<const bf16x8*>(dyr + i);
-    bf16x8 xv = *reinterpret_cast<const bf16x8*>(xr + i);
-    bf16x8 wv = *reinterpret_cast<const bf16x8*>(w + i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float wdy = bf2f(dv[j]) * bf2f(wv[j]);
-      float xhat = (bf2f(xv[j]) - mean) * rstd;
-      c1 += wdy;
-      c2 += wdy * xhat;
-    }
-  }
-  c1 = block_reduce_sum(c1, red) / H;
-  c2 = block_reduce_sum(c2, red) / H;
-
-  for (int i = threadIdx.x * 8; i < H; i += LN_BLOCK * 8) {
-    bf16x8 dv = *reinterpret_cast<const bf16x8*>(dyr + i);
-    bf16x8 xv = *reinterpret_cast<const bf16x8*>(xr + i);
-    bf16x8 wv = *reinterpret_cast<const bf16x8*>(w + i);
-    bf16x8 hv;
-    if (dhr != nullptr)
-      hv = *reinterpret_cast<const bf16x8*>(dhr + i);
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float wdy = bf2f(dv[j]) * bf2f(wv[j]);
-      float xhat = (bf2f(xv[j]) - mean) * rstd;
-      float g = (wdy - c1 - xhat * c2) * rstd;
-      if (dhr != nullptr) g += bf2f(hv[j]);
-      o[j] = f2bf(g);
-    }
-    *reinterpret_cast<bf16x8*>(dxr + i) = o;
-  }
-}
-
-extern "C" {
 
 hipError_t launch_add_layer_norm_fwd(const void* a, const void* b,
                                      const void* w, const void* bias,
@@ -354,18 +205,6 @@ hipError_t launch_add_layer_norm_fwd(const void* a, const void* b,
                               stream>>>(
       (const short*)a, (const short*)b, (const short*)w, (const short*)bias,
       (short*)h, (short*)y, mean, rstd, (int)H, eps);
-  return hipGetLastError();
-}
-
-hipError_t launch_add_layer_norm_bwd_dx(const void* dy, const void* dh,
-                                        const void* x, const void* w,
-                                        const float* mean, const float* rstd,
-                                        void* dx, int64_t N, int64_t H,
-                                        hipStream_t stream) {
-  add_layer_norm_bwd_dx_kernel<<<dim3((uint32_t)N), dim3(LN_BLOCK), 0,
-                                 stream>>>(
-      (const short*)dy, (const short*)dh, (const short*)x, (const short*)w,
-      mean, rstd, (short*)dx, (int)H);
   return hipGetLastError();
 }
 

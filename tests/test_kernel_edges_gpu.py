@@ -192,6 +192,51 @@ def test_add_layer_norm_hostile_values(ext, H, with_delta):
     _check_hostile(y, mean, rstd, h.double(), w.double(), b.double())
 
 
+# ------------------------------------------- plain and add LayerNorm agree
+
+_BITS = {2: torch.int16, 4: torch.int32}
+
+
+def _same_bytes(got, want, what):
+    """Bit patterns, so NaNs and signed zeros count."""
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    assert torch.equal(got.view(_BITS[got.dtype.itemsize]),
+                       want.view(_BITS[want.dtype.itemsize])), what
+
+
+# One thread only / idle threads / thread 0 takes a second trip / the model
+# width; N stays small because rows are independent.  Then the hostile rows.
+_SHARING_SHAPES = [(1, 8), (3, 1000), (3, 2056), (17, 2560)]
+
+
+def _sharing_inputs(case):
+    if case != "hostile":
+        return _ln_inputs(*case, 120)
+    base, pert = _hostile_rows(1000, 110)
+    g = _gen(121)
+    return ((base + pert).to(BF16).cuda(), _randn_bf16(g, 1000),
+            _randn_bf16(g, 1000), _randn_bf16(g, 6, 1000))
+
+
+@pytest.mark.parametrize("case", _SHARING_SHAPES + ["hostile"],
+                         ids=lambda c: c if isinstance(c, str)
+                         else f"{c[0]}x{c[1]}")
+def test_layer_norm_and_add_layer_norm_share_bytes(ext, case):
+    """layer_norm_fwd/bwd are add_layer_norm_fwd/bwd without delta/dh, to
+    the bit: both run the same row routine and the same dx kernel."""
+    x, w, b, dy = _sharing_inputs(case)
+    y, mean, rstd = ext.layer_norm_fwd(x, w, b, EPS)
+    h, y2, mean2, rstd2 = ext.add_layer_norm_fwd(x, None, w, b, EPS)
+    _same_bytes(h, x, "h")
+    _same_bytes(y2, y, "y")
+    _same_bytes(mean2, mean, "mean")
+    _same_bytes(rstd2, rstd, "rstd")
+    got = ext.add_layer_norm_bwd(dy, None, x, w, mean, rstd)
+    want = ext.layer_norm_bwd(dy, x, w, mean, rstd)
+    for g, t, what in zip(got, want, ("dx", "dw", "db")):
+        _same_bytes(g, t, what)
+
+
 # ------------------------------------------------------------------ bias+GeLU
 
 _GELU_SPECIALS = [0.0, -0.0, 6.0, -6.0, 30.0, -30.0, 200.0, -200.0, 1e4,
@@ -516,8 +561,11 @@ def test_fp8_quantize_single_layout(ext, numel, e5m2):
 
 
 @pytest.mark.parametrize("e5m2", [False, True])
-@pytest.mark.parametrize("M,N", [(1, 8), (64, 64), (65, 201), (130, 63)])
+@pytest.mark.parametrize("M,N", [(1, 8), (64, 64), (65, 201), (130, 63),
+                                 (130, 72), (72, 130)])
 def test_fp8_quantize_dual_layout(ext, M, N, e5m2):
+    """(130, 72) and (72, 130) have an interior tile whose q pitch,
+    respectively qt pitch, is 8 mod 16: whole tile, but no 16-byte stores."""
     x = _fp8_input((M, N), 161)
     scale = torch.tensor([_fp8_meta(e5m2)[2]], device="cuda")
     q, qt, amax = ext.fp8_quantize(x, scale, True, e5m2)
