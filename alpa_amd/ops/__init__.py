@@ -5,9 +5,11 @@ built from ``csrc/``); CPU tensors -> the pure-torch reference
 (`reference.py`).  Plain unfused GEMMs go through ``torch.matmul``
 (hipBLASLt on ROCm) — hand-written kernels cover the *fused* ops where
 library calls can't: LayerNorm, flash attention, bias+GeLU epilogue,
-softmax-cross-entropy over the 51200-wide vocab, multi-tensor AdamW with
-global-norm gradient clipping (multi_tensor_sumsq feeds fused_adamw), and
-the sync-free top-2 MoE routing path: moe_top2_route (gate + capacity
+softmax-cross-entropy over the 51200-wide vocab and over its tensor-parallel
+shards (softmax_cross_entropy_partial / _combine / _shard_bwd: per-shard
+row statistics, one [N]-sized combine, a collective-free backward),
+multi-tensor AdamW with global-norm gradient clipping (multi_tensor_sumsq
+feeds fused_adamw), and the sync-free top-2 MoE routing path: moe_top2_route (gate + capacity
 slots), moe_dispatch and moe_combine.  add_layer_norm_fp8 and bias_gelu_fp8
 are the LayerNorm and GeLU forwards with the fp8 quantize of ops/fp8.py
 folded in.
@@ -29,7 +31,9 @@ from ._backend import hip_ops, hip_ops_available, use_hip
 __all__ = [
     "layer_norm", "add_layer_norm", "bias_gelu", "add_layer_norm_fp8",
     "bias_gelu_fp8", "flash_attention",
-    "flash_attention_qkv", "softmax_cross_entropy", "fused_adamw",
+    "flash_attention_qkv", "softmax_cross_entropy",
+    "softmax_cross_entropy_partial", "softmax_cross_entropy_combine",
+    "softmax_cross_entropy_shard_bwd", "vocab_ce_fused_ok", "fused_adamw",
     "multi_tensor_sumsq",
     "hip_ops_available", "MoERouting", "moe_top2_route", "moe_dispatch",
     "moe_combine", "moe_fused_ok",
@@ -429,6 +433,70 @@ def softmax_cross_entropy(logits: torch.Tensor,
     softmax in fp32 [N, 51200].
     """
     return _SoftmaxCrossEntropy.apply(logits, targets)
+
+
+# The loss over a vocab-sharded LM head, in three pieces that carry no
+# autograd of their own: parallel.layers.fused_vocab_parallel_cross_entropy
+# puts the one collective between the first two and is the autograd user.
+
+
+def vocab_ce_fused_ok(logits: torch.Tensor) -> bool:
+    """Envelope of the vocab-shard loss kernels (csrc/cross_entropy.hip; the
+    bindings check the same): a contiguous 2-D bf16 shard on the GPU whose
+    width is a multiple of 8 and whose data is 16-byte aligned, for the
+    16-byte row loads."""
+    if not (logits.is_cuda and logits.dtype == torch.bfloat16):
+        return False
+    if logits.dim() != 2 or not logits.is_contiguous():
+        return False
+    if logits.shape[-1] < 8 or logits.shape[-1] % 8 != 0 or \
+            logits.data_ptr() % 16 != 0:
+        return False
+    return use_hip(logits)
+
+
+@torch.no_grad()
+def softmax_cross_entropy_partial(logits: torch.Tensor,
+                                  targets: torch.Tensor,
+                                  vocab_start: int) -> torch.Tensor:
+    """Row statistics of one vocab shard, logits [N, Vs] = global columns
+    [vocab_start, vocab_start + Vs), targets [N] global ids: stats [3, N]
+    = (row max m, s = sum exp(x - m), t = target logit if the shard owns
+    the target else 0).  A row of -inf only gives m = -inf, s = 0.  fp32 on
+    the GPU: one read of the shard, bit-reproducible, no read-back, and a
+    target outside the shard (negative or past the vocab too) is never
+    used as an index."""
+    if use_hip(logits):
+        return hip_ops().cross_entropy_partial_fwd(
+            logits.contiguous(), targets.contiguous(), int(vocab_start))
+    return ref.softmax_cross_entropy_partial(logits, targets,
+                                             int(vocab_start))
+
+
+@torch.no_grad()
+def softmax_cross_entropy_combine(stats: torch.Tensor):
+    """stats [T, 3, N], the partial statistics of T shards in rank order ->
+    (loss [N], lse [N]) over the whole vocab.  [N]-sized elementwise work
+    in a fixed (rank) order on either device, so ranks holding the same
+    gathered stats agree bit for bit.  A row that is -inf on every shard
+    is undefined."""
+    return ref.softmax_cross_entropy_combine(stats)
+
+
+@torch.no_grad()
+def softmax_cross_entropy_shard_bwd(dloss: torch.Tensor,
+                                    logits: torch.Tensor,
+                                    targets: torch.Tensor, lse: torch.Tensor,
+                                    vocab_start: int) -> torch.Tensor:
+    """dlogits [N, Vs] of one vocab shard from the whole-vocab lse [N]:
+    (exp(x - lse) - onehot) * dloss, the one-hot only on the shard that
+    owns the target.  A -inf logit gets exactly 0."""
+    if use_hip(logits):
+        return hip_ops().cross_entropy_shard_bwd(
+            dloss.contiguous(), logits.contiguous(), targets.contiguous(),
+            lse, int(vocab_start))
+    return ref.softmax_cross_entropy_shard_bwd(dloss, logits, targets, lse,
+                                               int(vocab_start))
 
 
 _ADAM_CHUNK = 16384  # must match ADAM_CHUNK in csrc/adamw.hip

@@ -351,7 +351,58 @@ at::Tensor cross_entropy_bwd(const at::Tensor& dloss, const at::Tensor& logits,
   HIP_OK(launch_ce_bwd((const float*)dl.const_data_ptr(), logits.const_data_ptr(),
                        (const int64_t*)targets.const_data_ptr(),
                        (const float*)lse.const_data_ptr(),
-                       dlogits.mutable_data_ptr(), N, V, cur_stream()));
+                       dlogits.mutable_data_ptr(), N, V, 0, cur_stream()));
+  return dlogits;
+}
+
+// One rank's vocab shard: logits bf16 [N, Vs] read with 16-byte loads,
+// targets int64 [N] of global vocab ids, the shard's first id.
+void check_ce_shard(const at::Tensor& logits, const at::Tensor& targets,
+                    int64_t vocab_start) {
+  check_bf16_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits must be 2-D [N, Vs]");
+  TORCH_CHECK(logits.size(1) > 0 && logits.size(1) % 8 == 0,
+              "Vs must be a positive multiple of 8");
+  TORCH_CHECK((uintptr_t)logits.const_data_ptr() % 16 == 0,
+              "logits must be 16-byte aligned");
+  TORCH_CHECK(targets.is_cuda() && targets.scalar_type() == at::kLong &&
+                  targets.is_contiguous() &&
+                  targets.numel() == logits.size(0),
+              "targets must be contiguous int64 [N] on GPU");
+  TORCH_CHECK(vocab_start >= 0, "vocab_start must be >= 0");
+}
+
+at::Tensor cross_entropy_partial_fwd(const at::Tensor& logits,
+                                     const at::Tensor& targets,
+                                     int64_t vocab_start) {
+  check_ce_shard(logits, targets, vocab_start);
+  int64_t N = logits.size(0), V = logits.size(1);
+  auto stats = at::empty({3, N}, logits.options().dtype(at::kFloat));
+  HIP_OK(launch_ce_partial_fwd(logits.const_data_ptr(),
+                               (const int64_t*)targets.const_data_ptr(),
+                               (float*)stats.mutable_data_ptr(), N, V,
+                               vocab_start, cur_stream()));
+  return stats;
+}
+
+at::Tensor cross_entropy_shard_bwd(const at::Tensor& dloss,
+                                   const at::Tensor& logits,
+                                   const at::Tensor& targets,
+                                   const at::Tensor& lse,
+                                   int64_t vocab_start) {
+  check_ce_shard(logits, targets, vocab_start);
+  int64_t N = logits.size(0), V = logits.size(1);
+  check_row_stats(lse, "lse", N);
+  TORCH_CHECK(dloss.is_cuda() && dloss.numel() == N,
+              "dloss must be [N] on GPU");
+  auto dlogits = at::empty_like(logits);
+  auto dl = dloss.to(at::kFloat).contiguous();
+  HIP_OK(launch_ce_bwd((const float*)dl.const_data_ptr(),
+                       logits.const_data_ptr(),
+                       (const int64_t*)targets.const_data_ptr(),
+                       (const float*)lse.const_data_ptr(),
+                       dlogits.mutable_data_ptr(), N, V, vocab_start,
+                       cur_stream()));
   return dlogits;
 }
 
@@ -874,7 +925,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // 5: multi_tensor_sumsq_raw added; adamw_step_raw takes grad_sumsq and
   // max_grad_norm
   // 6: bias_gelu_fp8 and add_layer_norm_fp8 added
-  m.attr("ABI_VERSION") = 6;
+  // 7: cross_entropy_partial_fwd and cross_entropy_shard_bwd added
+  m.attr("ABI_VERSION") = 7;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)");
   m.def("add_layer_norm_fwd", &add_layer_norm_fwd,
@@ -901,6 +953,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "residual-add + LayerNorm fwd emitting e4m3 q, qt and amax (gfx950)");
   m.def("cross_entropy_fwd", &cross_entropy_fwd, "fused CE fwd (gfx950)");
   m.def("cross_entropy_bwd", &cross_entropy_bwd, "fused CE bwd (gfx950)");
+  m.def("cross_entropy_partial_fwd", &cross_entropy_partial_fwd,
+        "vocab-shard CE partial stats [3, N] (gfx950)");
+  m.def("cross_entropy_shard_bwd", &cross_entropy_shard_bwd,
+        "vocab-shard CE bwd (gfx950)");
   m.def("attn_fwd", &attn_fwd, "flash attention fwd (gfx950 MFMA)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
         py::arg("scale"), py::arg("alibi") = py::none(),

@@ -89,10 +89,16 @@ hipError_t launch_skinny_gemm(const void* wp, const void* x, float* part,
 hipError_t launch_ce_fwd(const void* logits, const int64_t* targets,
                          float* loss, float* lse, int64_t N, int64_t V,
                          hipStream_t stream);
+// vocab shard [N, V] holding global columns [vocab_start, vocab_start + V);
+// stats: fp32 [3, N] = (row max, sum exp(x - max), owned target logit or 0)
+hipError_t launch_ce_partial_fwd(const void* logits, const int64_t* targets,
+                                 float* stats, int64_t N, int64_t V,
+                                 int64_t vocab_start, hipStream_t stream);
+// the full vocab is the shard with vocab_start = 0
 hipError_t launch_ce_bwd(const float* dloss, const void* logits,
                          const int64_t* targets, const float* lse,
                          void* dlogits, int64_t N, int64_t V,
-                         hipStream_t stream);
+                         int64_t vocab_start, hipStream_t stream);
 
 // ---- attention.hip ----
 // strides: q(3) k(3) v(3) o(3), each (batch, head, seq) in elements

@@ -225,6 +225,63 @@ def softmax_cross_entropy_bwd(dloss: torch.Tensor, logits: torch.Tensor,
     return (p * _up(dloss).unsqueeze(-1)).to(logits.dtype)
 
 
+def _shard_target(targets: torch.Tensor, vocab_start: int, width: int):
+    """(owned [N] bool, column [N]) of global target ids inside the vocab
+    shard [vocab_start, vocab_start + width); the column of a target the
+    shard does not own is clamped into range and must not be used."""
+    local = targets - vocab_start
+    owned = (local >= 0) & (local < width)
+    return owned, local.clamp(0, width - 1)
+
+
+def softmax_cross_entropy_partial(logits: torch.Tensor, targets: torch.Tensor,
+                                  vocab_start: int) -> torch.Tensor:
+    """Combinable row statistics of one vocab shard: logits [N, Vs] holds
+    global columns [vocab_start, vocab_start + Vs), targets [N] are global
+    ids.  Returns stats [3, N]: the shard's row max m (-inf for a row of
+    -inf only), s = sum exp(x - m) (0 where m = -inf) and t = the target
+    logit where the shard owns the target, else 0."""
+    lf = _up(logits)
+    m = lf.max(dim=-1).values
+    # a fully masked row: shift by 0, every exp(-inf) is 0
+    shift = torch.where(torch.isinf(m) & (m < 0), torch.zeros_like(m), m)
+    s = torch.exp(lf - shift.unsqueeze(-1)).sum(dim=-1)
+    owned, col = _shard_target(targets, vocab_start, lf.shape[-1])
+    t = lf.gather(-1, col.unsqueeze(-1)).squeeze(-1)
+    t = torch.where(owned, t, torch.zeros_like(t))
+    return torch.stack([m, s, t])
+
+
+def softmax_cross_entropy_combine(stats: torch.Tensor
+                                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """stats [T, 3, N], the partial statistics of T vocab shards in rank
+    order -> (loss [N], lse [N]) over the whole vocab.  The sums run in
+    rank order, so every rank that holds the same stats gets the same
+    bits.  A shard with m = -inf adds nothing; a row masked on every shard
+    is undefined."""
+    m, s, t = stats[:, 0], stats[:, 1], stats[:, 2]
+    gm = m.max(dim=0).values
+    # s = 0 wherever m = -inf, and exp(-inf - gm) = 0: the product is 0
+    w = s * torch.exp(m - gm)
+    gs, gt = w[0], t[0]
+    for r in range(1, stats.shape[0]):
+        gs = gs + w[r]
+        gt = gt + t[r]
+    lse = gm + torch.log(gs)
+    return lse - gt, lse
+
+
+def softmax_cross_entropy_shard_bwd(dloss: torch.Tensor, logits: torch.Tensor,
+                                    targets: torch.Tensor, lse: torch.Tensor,
+                                    vocab_start: int) -> torch.Tensor:
+    """dlogits of one vocab shard from the whole-vocab lse: (exp(x - lse) -
+    onehot) * dloss, the one-hot only where the shard owns the target."""
+    p = torch.exp(_up(logits) - lse.unsqueeze(-1))
+    owned, col = _shard_target(targets, vocab_start, logits.shape[-1])
+    p.scatter_add_(-1, col.unsqueeze(-1), -owned.to(p.dtype).unsqueeze(-1))
+    return (p * _up(dloss).unsqueeze(-1)).to(logits.dtype)
+
+
 def adamw_step(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float,
                beta1: float, beta2: float, eps: float, weight_decay: float,
                grad_scale: float = 1.0, grad_sumsq=None,

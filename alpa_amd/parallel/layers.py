@@ -371,13 +371,69 @@ class _VocabParallelCrossEntropy(torch.autograd.Function):
         return dlogits, None, None, None, None
 
 
+class _FusedVocabParallelCrossEntropy(torch.autograd.Function):
+    """Cross-entropy over vocab-sharded logits [N, V/tp] in one pass over
+    the shard and one collective.
+
+    Forward: per-shard row statistics (max, sum-exp, owned target logit),
+    one all-gather of the [3, N] statistics along the axis, then the same
+    rank-ordered combine on every rank, which therefore agree bit for bit.
+    Backward: dlogits from saved (logits, targets, global lse), locally.
+    """
+
+    @staticmethod
+    def forward(ctx, logits, targets, mesh: Optional[DeviceMesh], axis: int,
+                vocab_start: int):
+        logits = logits.contiguous()
+        stats = ops.softmax_cross_entropy_partial(logits, targets,
+                                                  vocab_start)
+        tp = mesh.axis_size(axis) if mesh is not None else 1
+        if tp == 1:
+            gathered = stats.unsqueeze(0)
+        else:
+            # gathered as the dim-0 concatenation [tp * 3, N], the one
+            # output layout every backend takes
+            gathered = stats.new_empty(tp * 3, stats.shape[1])
+            mesh.all_gather(gathered, stats, axis=axis)
+            gathered = gathered.view(tp, 3, -1)
+        loss, lse = ops.softmax_cross_entropy_combine(gathered)
+        ctx.save_for_backward(logits, targets, lse)
+        ctx.vocab_start = vocab_start
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, targets, lse = ctx.saved_tensors
+        dlogits = ops.softmax_cross_entropy_shard_bwd(
+            dloss, logits, targets, lse, ctx.vocab_start)
+        return dlogits, None, None, None, None
+
+
+def fused_vocab_parallel_cross_entropy(logits: torch.Tensor,
+                                       targets: torch.Tensor,
+                                       mesh: Optional[DeviceMesh], axis: int,
+                                       vocab_start: int) -> torch.Tensor:
+    """Per-token loss [N] for vocab-sharded logits [N, V/tp] whose first
+    column is global vocab id `vocab_start`; targets [N] hold global ids.
+    Differentiable in logits.  On the GPU (see ops.vocab_ce_fused_ok for
+    the envelope) the shard is read once forward and once backward by the
+    gfx950 kernels and the only collective is one all-gather of 12 bytes
+    per token; CPU tensors take the reference functions."""
+    return _FusedVocabParallelCrossEntropy.apply(logits, targets, mesh, axis,
+                                                 vocab_start)
+
+
 def vocab_parallel_cross_entropy(logits: torch.Tensor, targets: torch.Tensor,
                                  mesh: Optional[DeviceMesh], axis: int,
                                  vocab_start: int) -> torch.Tensor:
     """Per-token loss for vocab-sharded logits. Falls back to the fused
-    single-device kernel when tp == 1."""
+    single-device kernel when tp == 1; at tp > 1 takes the fused shard
+    kernels where they apply and the torch path everywhere else."""
     if mesh is None or mesh.axis_size(axis) == 1:
         return ops.softmax_cross_entropy(logits, targets)
+    if ops.vocab_ce_fused_ok(logits):
+        return fused_vocab_parallel_cross_entropy(logits, targets, mesh, axis,
+                                                  vocab_start)
     return _VocabParallelCrossEntropy.apply(logits, targets, mesh, axis,
                                             vocab_start)
 

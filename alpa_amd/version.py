@@ -11,9 +11,10 @@ from __future__ import annotations
 
 __version__ = "0.1.0"
 
-#: minimum extension ABI this Python tree can drive (6: bias_gelu_fp8 and
-#: add_layer_norm_fp8, which the default fp8 training route calls)
-MIN_HIP_OPS_ABI = 6
+#: minimum extension ABI this Python tree can drive (7:
+#: cross_entropy_partial_fwd and cross_entropy_shard_bwd, which the loss
+#: calls whenever the vocab is sharded over tp > 1)
+MIN_HIP_OPS_ABI = 7
 
 
 def check_hip_ops_version() -> int:
