@@ -20,6 +20,7 @@ grad accumulation, collectives).
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import List, NamedTuple, Optional
 
@@ -774,21 +775,29 @@ def moe_fused_ok(x: torch.Tensor, num_experts: int,
 
 # ----------------------------- skinny decode GEMM --------------------------
 
-import functools
+def _skinny_mt(M: int) -> int:
+    """The kernel's padded-M tier: the power of two >= max(M, 4)."""
+    MT = 4
+    while MT < M:
+        MT *= 2
+    return MT
+
+
+def _skinny_legal_splits(K: int, MT: int) -> List[int]:
+    """Ascending split-K factors the kernel takes: s divides K/64 (keeps
+    rounds = K/8/s a multiple of the 8-deep pipeline) and the LDS x-slice
+    (rounds * 16 * MT bytes) fits 64 KB."""
+    q = K // 64
+    return [s for s in range(1, q + 1)
+            if q % s == 0 and (K // 8 // s) * 16 * MT <= 65536]
 
 
 @functools.lru_cache(maxsize=None)
 def _skinny_splits(N: int, K: int, M: int) -> Optional[int]:
-    """Split-K factor for the decode GEMV: s must divide K/64 (keeps
-    rounds a multiple of the kernel's 8-deep pipeline), the LDS x-slice
-    (rounds * 16 * MT bytes) must fit 64 KB, and the grid (N/64 x s)
-    should fill the 256 CUs.  None = shapes unsupported."""
-    MT = 4
-    while MT < M:
-        MT *= 2
-    q = K // 64
-    lds_ok = [s for s in range(1, q + 1)
-              if q % s == 0 and (K // 8 // s) * 16 * MT <= 65536]
+    """Split-K factor for the decode GEMV: a legal split
+    (_skinny_legal_splits) whose grid (N/64 x s) should fill the 256 CUs.
+    None = shapes unsupported."""
+    lds_ok = _skinny_legal_splits(K, _skinny_mt(M))
     if not lds_ok:
         return None
     # sweep-tuned (tools/skinny_bench.py): ~16 k-rounds per workgroup is
@@ -874,9 +883,7 @@ def _skinny_tune(wp, x2, scale, N, K, MT):
     got = _SKINNY_TUNED.get(key)
     if got is not None:
         return got
-    q = K // 64
-    legal = [c for c in range(1, q + 1)
-             if q % c == 0 and (K // 8 // c) * 16 * MT <= 65536]
+    legal = _skinny_legal_splits(K, MT)
     cands = sorted({
         s for s in (
             next((c for c in reversed(legal)
@@ -908,8 +915,9 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
                   bias: Optional[torch.Tensor], module) -> torch.Tensor:
     """y = x @ W^T (+bias) through the packed decode GEMV.  fp8 weights
     (half the bytes/token) when global_config.fp8_gemm is on and the
-    module isn't _fp8_exclude; split-K fp32 accumulation (atomicAdd
-    order nondeterministic — inference only)."""
+    module isn't _fp8_exclude; split-K fp32 partials are stored and
+    reduced in a fixed order by a finalize launch (deterministic, no
+    atomics).  Inference only."""
     from ..global_env import global_config
     fp8 = (global_config.fp8_gemm and
            not getattr(module, "_fp8_exclude", False))
@@ -918,9 +926,7 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
     shape = x.shape
     x2 = x.reshape(-1, K).contiguous()
     b = bias.contiguous() if bias is not None else None
-    MT = 4
-    while MT < x2.shape[0]:
-        MT *= 2
+    MT = _skinny_mt(x2.shape[0])
     if torch.cuda.is_current_stream_capturing():
         splits = _SKINNY_TUNED.get((N, K, MT, scale is not None)) \
             or _skinny_splits(N, K, x2.shape[0])

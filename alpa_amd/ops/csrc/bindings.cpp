@@ -27,34 +27,95 @@ hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStream().stream();
 }
 
-void check_bf16_contig(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+// ---------------------------- operand checks -----------------------------
+// Every entry below examines every tensor it hands to a launcher with one of
+// these, before it allocates or launches.  `first` is the entry's first
+// tensor operand (itself, for that operand): all operands share its device.
+
+const char* dtype_name(at::ScalarType dtype) {
+  switch (dtype) {
+    case at::kBFloat16: return "bf16";
+    case at::kFloat: return "fp32";
+    case at::kInt: return "int32";
+    case at::kLong: return "int64";
+    default: return c10::toString(dtype);
+  }
 }
 
-// per-feature vector (LayerNorm weight/bias, GeLU bias): bf16 [n]; the
-// kernels read it with 16-byte loads straight off the raw pointer
-void check_bf16_vec(const at::Tensor& t, const char* name, int64_t n) {
-  check_bf16_contig(t, name);
+// on the GPU, on the device of the first operand
+void check_device(const at::Tensor& t, const char* name,
+                  const at::Tensor& first) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.device() == first.device(), name, " is on ", t.device(),
+              " but the first operand is on ", first.device());
+}
+
+// a device operand of one scalar type
+void check_typed(const at::Tensor& t, const char* name, at::ScalarType dtype,
+                 const at::Tensor& first) {
+  check_device(t, name, first);
+  TORCH_CHECK(t.scalar_type() == dtype, name, " must be ", dtype_name(dtype));
+}
+
+// a vector or statistics tensor: contiguous, n elements of one type (bf16
+// per-feature vectors read with 16-byte loads, fp32 row statistics and
+// scalars, int32/int64 index vectors)
+void check_vec(const at::Tensor& t, const char* name, at::ScalarType dtype,
+               int64_t n, const at::Tensor& first) {
+  check_typed(t, name, dtype, first);
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
   TORCH_CHECK(t.numel() == n, name, " must have ", n, " elements, got ",
               t.numel());
 }
 
-// saved per-row statistics: fp32 [N]
-void check_row_stats(const at::Tensor& t, const char* name, int64_t N) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be fp32");
-  TORCH_CHECK(t.is_contiguous() && t.numel() == N, name,
-              " must be contiguous [N]");
+// row-major bf16 rows [.., W] with W a positive multiple of m (8 for the
+// kernels that read rows with 16-byte loads); returns (N, W).  The only
+// place that divides numel() by a width: W > 0 is checked just above it.
+std::pair<int64_t, int64_t> check_rows(const at::Tensor& t, const char* name,
+                                       int64_t m, const at::Tensor& first) {
+  check_typed(t, name, at::kBFloat16, first);
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.dim() >= 1, name, " must have a feature dimension");
+  const int64_t W = t.size(-1);
+  TORCH_CHECK(W > 0 && W % m == 0, name,
+              ": the last dimension must be a positive multiple of ", m,
+              ", got ", W);
+  return {t.numel() / W, W};
 }
 
-// a second [.., H] operand that the kernel indexes exactly like `ref`
-void check_same_shape(const at::Tensor& t, const char* name,
-                      const at::Tensor& ref, const char* ref_name) {
-  check_bf16_contig(t, name);
+// a second bf16 operand that the kernel indexes exactly like `ref`
+void check_like(const at::Tensor& t, const char* name, const at::Tensor& ref,
+                const char* ref_name) {
+  check_typed(t, name, at::kBFloat16, ref);
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
   TORCH_CHECK(t.sizes() == ref.sizes(), name, " must have the shape of ",
               ref_name);
+}
+
+// a logical [B, H, S, D] bf16 view with arbitrary B/H/S strides and a
+// contiguous D; a negative expected size accepts any
+void check_bhsd(const at::Tensor& t, const char* name, int64_t B, int64_t H,
+                int64_t S, int64_t D, const at::Tensor& first) {
+  check_typed(t, name, at::kBFloat16, first);
+  TORCH_CHECK(t.dim() == 4, name, " must be 4-D [B,H,S,D]");
+  TORCH_CHECK(t.stride(3) == 1, name, " head-dim must be contiguous");
+  const int64_t want[4] = {B, H, S, D};
+  for (int i = 0; i < 4; ++i)
+    TORCH_CHECK(want[i] < 0 || t.size(i) == want[i], name, " must have size ",
+                want[i], " in dimension ", i, ", got ", t.size(i));
+}
+
+// 2-D bf16 rows [N, W], W a positive multiple of 8, at a 16-byte-aligned
+// address: the vocab-shard CE and MoE entries, whose callers promise the
+// alignment.  Returns (N, W).
+std::pair<int64_t, int64_t> check_aligned_rows(const at::Tensor& t,
+                                               const char* name,
+                                               const at::Tensor& first) {
+  auto dims = check_rows(t, name, 8, first);
+  TORCH_CHECK(t.dim() == 2, name, " must be 2-D");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.const_data_ptr()) % 16 == 0, name,
+              " must be 16-byte aligned");
+  return dims;
 }
 
 // Deterministic column-partial stripe count: enough (stripes x column
@@ -74,12 +135,9 @@ int stripes_for(int64_t N, int64_t cols, int64_t chunk_cols) {
 std::vector<at::Tensor> layer_norm_fwd(const at::Tensor& x,
                                        const at::Tensor& w,
                                        const at::Tensor& b, double eps) {
-  check_bf16_contig(x, "x");
-  int64_t H = x.size(-1);
-  int64_t N = x.numel() / H;
-  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
-  check_bf16_vec(w, "w", H);
-  check_bf16_vec(b, "b", H);
+  auto [N, H] = check_rows(x, "x", 8, x);
+  check_vec(w, "w", at::kBFloat16, H, x);
+  check_vec(b, "b", at::kBFloat16, H, x);
   auto y = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
   auto mean = at::empty({N}, f32);
@@ -122,14 +180,11 @@ std::vector<at::Tensor> layer_norm_bwd(const at::Tensor& dy,
                                        const at::Tensor& w,
                                        const at::Tensor& mean,
                                        const at::Tensor& rstd) {
-  check_bf16_contig(x, "x");
-  check_same_shape(dy, "dy", x, "x");
-  int64_t H = x.size(-1);
-  int64_t N = x.numel() / H;
-  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
-  check_bf16_vec(w, "w", H);
-  check_row_stats(mean, "mean", N);
-  check_row_stats(rstd, "rstd", N);
+  auto [N, H] = check_rows(x, "x", 8, x);
+  check_like(dy, "dy", x, "x");
+  check_vec(w, "w", at::kBFloat16, H, x);
+  check_vec(mean, "mean", at::kFloat, N, x);
+  check_vec(rstd, "rstd", at::kFloat, N, x);
   auto dx = at::empty_like(x);
   HIP_OK(launch_layer_norm_bwd_dx(
       dy.const_data_ptr(), nullptr, x.const_data_ptr(), w.const_data_ptr(),
@@ -146,13 +201,10 @@ std::vector<at::Tensor> add_layer_norm_fwd(const at::Tensor& a,
                                            const at::Tensor& w,
                                            const at::Tensor& bias,
                                            double eps) {
-  check_bf16_contig(a, "a");
-  int64_t H = a.size(-1);
-  int64_t N = a.numel() / H;
-  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
-  if (b.has_value()) check_same_shape(*b, "b", a, "a");
-  check_bf16_vec(w, "w", H);
-  check_bf16_vec(bias, "bias", H);
+  auto [N, H] = check_rows(a, "a", 8, a);
+  if (b.has_value()) check_like(*b, "b", a, "a");
+  check_vec(w, "w", at::kBFloat16, H, a);
+  check_vec(bias, "bias", at::kBFloat16, H, a);
   auto h = at::empty_like(a);
   auto y = at::empty_like(a);
   auto f32 = a.options().dtype(at::kFloat);
@@ -171,15 +223,12 @@ std::vector<at::Tensor> add_layer_norm_bwd(
     const at::Tensor& dy, const c10::optional<at::Tensor>& dh,
     const at::Tensor& h, const at::Tensor& w, const at::Tensor& mean,
     const at::Tensor& rstd) {
-  check_bf16_contig(h, "h");
-  check_same_shape(dy, "dy", h, "h");
-  if (dh.has_value()) check_same_shape(*dh, "dh", h, "h");
-  int64_t H = h.size(-1);
-  int64_t N = h.numel() / H;
-  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
-  check_bf16_vec(w, "w", H);
-  check_row_stats(mean, "mean", N);
-  check_row_stats(rstd, "rstd", N);
+  auto [N, H] = check_rows(h, "h", 8, h);
+  check_like(dy, "dy", h, "h");
+  if (dh.has_value()) check_like(*dh, "dh", h, "h");
+  check_vec(w, "w", at::kBFloat16, H, h);
+  check_vec(mean, "mean", at::kFloat, N, h);
+  check_vec(rstd, "rstd", at::kFloat, N, h);
   auto dx = at::empty_like(h);
   const void* dhp = dh.has_value() ? dh->const_data_ptr() : nullptr;
   HIP_OK(launch_layer_norm_bwd_dx(
@@ -194,11 +243,8 @@ std::vector<at::Tensor> add_layer_norm_bwd(
 // ------------------------------- BiasGelu --------------------------------
 
 at::Tensor bias_gelu_fwd(const at::Tensor& x, const at::Tensor& bias) {
-  check_bf16_contig(x, "x");
-  int64_t F = x.size(-1);
-  int64_t N = x.numel() / F;
-  TORCH_CHECK(F % 8 == 0, "F must be a multiple of 8");
-  check_bf16_vec(bias, "bias", F);
+  auto [N, F] = check_rows(x, "x", 8, x);
+  check_vec(bias, "bias", at::kBFloat16, F, x);
   auto y = at::empty_like(x);
   HIP_OK(launch_bias_gelu_fwd(x.const_data_ptr(), bias.const_data_ptr(),
                               y.mutable_data_ptr(), N, F, cur_stream()));
@@ -208,12 +254,9 @@ at::Tensor bias_gelu_fwd(const at::Tensor& x, const at::Tensor& bias) {
 std::vector<at::Tensor> bias_gelu_bwd(const at::Tensor& dy,
                                       const at::Tensor& x,
                                       const at::Tensor& bias) {
-  check_bf16_contig(x, "x");
-  check_same_shape(dy, "dy", x, "x");
-  int64_t F = x.size(-1);
-  int64_t N = x.numel() / F;
-  TORCH_CHECK(F % 8 == 0, "F must be a multiple of 8");
-  check_bf16_vec(bias, "bias", F);
+  auto [N, F] = check_rows(x, "x", 8, x);
+  check_like(dy, "dy", x, "x");
+  check_vec(bias, "bias", at::kBFloat16, F, x);
   auto dx = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
   const int kStripes = stripes_for(N, F, 2048);
@@ -231,9 +274,8 @@ std::vector<at::Tensor> bias_gelu_bwd(const at::Tensor& dy,
 // at::sum): the bias-gradient reduction for plain +bias layers (the
 // at::native reduce path cost ~8 ms/step in the r2 profile)
 at::Tensor colsum_bf16(const at::Tensor& t) {
-  check_bf16_contig(t, "t");
-  int64_t F = t.size(-1);
-  int64_t N = t.numel() / F;
+  // any positive width: the kernel has a scalar tail
+  auto [N, F] = check_rows(t, "t", 1, t);
   auto f32 = t.options().dtype(at::kFloat);
   const int kStripes = stripes_for(N, F, 2048);
   auto part = at::empty({kStripes, F}, f32);
@@ -255,13 +297,29 @@ at::Tensor skinny_gemm(const at::Tensor& wp, const at::Tensor& x,
                        const c10::optional<at::Tensor>& wscale,
                        const c10::optional<at::Tensor>& bias,
                        int64_t N, int64_t K, int64_t splits) {
-  TORCH_CHECK(wp.is_cuda() && x.is_cuda() && x.is_contiguous());
-  TORCH_CHECK(x.dim() == 2 && x.size(1) == K, "x must be [M, K]");
-  const int64_t M = x.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64, "skinny path is for M <= 64");
+  TORCH_CHECK(N > 0 && N % 64 == 0, "N must be a positive multiple of 64");
+  TORCH_CHECK(K > 0 && K % 64 == 0, "K must be a positive multiple of 64");
   const bool fp8 = wscale.has_value();
+  if (fp8) {
+    check_device(wp, "wp", wp);
+    TORCH_CHECK(wp.element_size() == 1,
+                "wp must hold one-byte elements when wscale is given");
+    TORCH_CHECK(wp.is_contiguous() && wp.numel() == N * K,
+                "wp must be contiguous with N*K elements");
+    check_vec(*wscale, "wscale", at::kFloat, 1, wp);
+  } else {
+    check_vec(wp, "wp", at::kBFloat16, N * K, wp);
+  }
+  if (bias.has_value()) check_vec(*bias, "bias", at::kBFloat16, N, wp);
+  auto [M, Kx] = check_rows(x, "x", 64, wp);
+  TORCH_CHECK(x.dim() == 2 && Kx == K, "x must be [M, K]");
+  TORCH_CHECK(M >= 1 && M <= 64, "skinny path is for M <= 64");
   int64_t MT = 4;
   while (MT < M) MT *= 2;
+  // what the kernel's 8-deep pipeline and its 64 KB LDS x-slice take
+  TORCH_CHECK(splits >= 1 && (K / 64) % splits == 0 &&
+                  (K / 8 / splits) * 16 * MT <= 65536,
+              "splits must divide K/64 and leave (K/8/splits)*16*MT <= 65536");
   at::Tensor xp = x;
   if (MT != M) {
     xp = at::zeros({MT, K}, x.options());
@@ -286,13 +344,14 @@ void adamw_step_raw(const at::Tensor& descs, const at::Tensor& chunks,
                     double eps, double weight_decay, double grad_scale,
                     const c10::optional<at::Tensor>& grad_sumsq,
                     double max_grad_norm) {
-  TORCH_CHECK(descs.is_cuda() && chunks.is_cuda());
+  TORCH_CHECK(descs.dim() == 2 && descs.size(1) == 6, "descs must be [n, 6]");
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 2,
+              "chunks must be [m, 2]");
+  check_vec(descs, "descs", at::kLong, descs.numel(), descs);
+  check_vec(chunks, "chunks", at::kInt, chunks.numel(), descs);
   const float* sumsq = nullptr;
   if (grad_sumsq.has_value()) {
-    TORCH_CHECK(grad_sumsq->is_cuda(), "grad_sumsq must be on GPU");
-    TORCH_CHECK(grad_sumsq->scalar_type() == at::kFloat,
-                "grad_sumsq must be fp32");
-    TORCH_CHECK(grad_sumsq->numel() == 1, "grad_sumsq must have 1 element");
+    check_vec(*grad_sumsq, "grad_sumsq", at::kFloat, 1, descs);
     TORCH_CHECK(max_grad_norm > 0, "max_grad_norm must be positive");
     sumsq = (const float*)grad_sumsq->const_data_ptr();
   }
@@ -307,14 +366,17 @@ void adamw_step_raw(const at::Tensor& descs, const at::Tensor& chunks,
 // partials: fp32 workspace [num_chunks]; out: fp32 [1]
 void multi_tensor_sumsq_raw(const at::Tensor& descs, const at::Tensor& chunks,
                             at::Tensor& partials, at::Tensor& out) {
-  TORCH_CHECK(descs.is_cuda() && chunks.is_cuda());
+  TORCH_CHECK(descs.dim() == 2 && descs.size(1) == 6, "descs must be [n, 6]");
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 2,
+              "chunks must be [m, 2]");
+  check_vec(descs, "descs", at::kLong, descs.numel(), descs);
+  check_vec(chunks, "chunks", at::kInt, chunks.numel(), descs);
   int64_t n = chunks.size(0);
-  TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
-                  partials.is_contiguous() && partials.numel() >= n,
-              "partials must be fp32 [num_chunks] on GPU");
-  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat &&
-                  out.numel() == 1,
-              "out must be fp32 [1] on GPU");
+  // the workspace may be longer than the chunk table
+  check_typed(partials, "partials", at::kFloat, descs);
+  TORCH_CHECK(partials.is_contiguous() && partials.numel() >= n,
+              "partials must be contiguous with at least num_chunks elements");
+  check_vec(out, "out", at::kFloat, 1, descs);
   HIP_OK(launch_multi_tensor_sumsq(
       descs.const_data_ptr(), chunks.const_data_ptr(), (int)n,
       (float*)partials.mutable_data_ptr(), (float*)out.mutable_data_ptr(),
@@ -325,11 +387,8 @@ void multi_tensor_sumsq_raw(const at::Tensor& descs, const at::Tensor& chunks,
 
 std::vector<at::Tensor> cross_entropy_fwd(const at::Tensor& logits,
                                           const at::Tensor& targets) {
-  check_bf16_contig(logits, "logits");
-  TORCH_CHECK(targets.scalar_type() == at::kLong);
-  int64_t V = logits.size(-1);
-  int64_t N = logits.numel() / V;
-  TORCH_CHECK(V % 8 == 0, "V must be a multiple of 8");
+  auto [N, V] = check_rows(logits, "logits", 8, logits);
+  check_vec(targets, "targets", at::kLong, N, logits);
   auto f32 = logits.options().dtype(at::kFloat);
   auto loss = at::empty({N}, f32);
   auto lse = at::empty({N}, f32);
@@ -343,9 +402,13 @@ std::vector<at::Tensor> cross_entropy_fwd(const at::Tensor& logits,
 at::Tensor cross_entropy_bwd(const at::Tensor& dloss, const at::Tensor& logits,
                              const at::Tensor& targets,
                              const at::Tensor& lse) {
-  check_bf16_contig(logits, "logits");
-  int64_t V = logits.size(-1);
-  int64_t N = logits.numel() / V;
+  auto [N, V] = check_rows(logits, "logits", 8, logits);
+  check_vec(targets, "targets", at::kLong, N, logits);
+  check_vec(lse, "lse", at::kFloat, N, logits);
+  // any dtype and layout: converted below
+  check_device(dloss, "dloss", logits);
+  TORCH_CHECK(dloss.numel() == N, "dloss must have ", N, " elements, got ",
+              dloss.numel());
   auto dlogits = at::empty_like(logits);
   auto dl = dloss.to(at::kFloat).contiguous();
   HIP_OK(launch_ce_bwd((const float*)dl.const_data_ptr(), logits.const_data_ptr(),
@@ -355,28 +418,14 @@ at::Tensor cross_entropy_bwd(const at::Tensor& dloss, const at::Tensor& logits,
   return dlogits;
 }
 
-// One rank's vocab shard: logits bf16 [N, Vs] read with 16-byte loads,
-// targets int64 [N] of global vocab ids, the shard's first id.
-void check_ce_shard(const at::Tensor& logits, const at::Tensor& targets,
-                    int64_t vocab_start) {
-  check_bf16_contig(logits, "logits");
-  TORCH_CHECK(logits.dim() == 2, "logits must be 2-D [N, Vs]");
-  TORCH_CHECK(logits.size(1) > 0 && logits.size(1) % 8 == 0,
-              "Vs must be a positive multiple of 8");
-  TORCH_CHECK((uintptr_t)logits.const_data_ptr() % 16 == 0,
-              "logits must be 16-byte aligned");
-  TORCH_CHECK(targets.is_cuda() && targets.scalar_type() == at::kLong &&
-                  targets.is_contiguous() &&
-                  targets.numel() == logits.size(0),
-              "targets must be contiguous int64 [N] on GPU");
-  TORCH_CHECK(vocab_start >= 0, "vocab_start must be >= 0");
-}
-
+// One rank's vocab shard: logits bf16 [N, Vs] = global columns
+// [vocab_start, vocab_start + Vs), targets int64 [N] of global vocab ids.
 at::Tensor cross_entropy_partial_fwd(const at::Tensor& logits,
                                      const at::Tensor& targets,
                                      int64_t vocab_start) {
-  check_ce_shard(logits, targets, vocab_start);
-  int64_t N = logits.size(0), V = logits.size(1);
+  auto [N, V] = check_aligned_rows(logits, "logits", logits);
+  check_vec(targets, "targets", at::kLong, N, logits);
+  TORCH_CHECK(vocab_start >= 0, "vocab_start must be >= 0");
   auto stats = at::empty({3, N}, logits.options().dtype(at::kFloat));
   HIP_OK(launch_ce_partial_fwd(logits.const_data_ptr(),
                                (const int64_t*)targets.const_data_ptr(),
@@ -390,11 +439,14 @@ at::Tensor cross_entropy_shard_bwd(const at::Tensor& dloss,
                                    const at::Tensor& targets,
                                    const at::Tensor& lse,
                                    int64_t vocab_start) {
-  check_ce_shard(logits, targets, vocab_start);
-  int64_t N = logits.size(0), V = logits.size(1);
-  check_row_stats(lse, "lse", N);
-  TORCH_CHECK(dloss.is_cuda() && dloss.numel() == N,
-              "dloss must be [N] on GPU");
+  auto [N, V] = check_aligned_rows(logits, "logits", logits);
+  check_vec(targets, "targets", at::kLong, N, logits);
+  TORCH_CHECK(vocab_start >= 0, "vocab_start must be >= 0");
+  check_vec(lse, "lse", at::kFloat, N, logits);
+  // any dtype and layout: converted below
+  check_device(dloss, "dloss", logits);
+  TORCH_CHECK(dloss.numel() == N, "dloss must have ", N, " elements, got ",
+              dloss.numel());
   auto dlogits = at::empty_like(logits);
   auto dl = dloss.to(at::kFloat).contiguous();
   HIP_OK(launch_ce_bwd((const float*)dl.const_data_ptr(),
@@ -407,13 +459,6 @@ at::Tensor cross_entropy_shard_bwd(const at::Tensor& dloss,
 }
 
 // ------------------------------ Attention --------------------------------
-
-void check_bf16_strided4(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
-  TORCH_CHECK(t.dim() == 4, name, " must be 4-D [B,H,S,D]");
-  TORCH_CHECK(t.stride(3) == 1, name, " head-dim must be contiguous");
-}
 
 // q/k/v/o are logical [B, H, S, D] views with arbitrary B/H/S strides and a
 // contiguous D — so the packed qkv layout [B, S, heads, 3*D] feeds the
@@ -429,25 +474,35 @@ std::array<int64_t, 3 * sizeof...(T)> bhs_strides(const T&... t) {
   return s;
 }
 
-// ALiBi slopes: optional per-head fp32 device tensor [H]; nullptr = off
-static const float* alibi_ptr(const c10::optional<at::Tensor>& alibi,
-                              int64_t H) {
-  if (!alibi.has_value() || !alibi->defined()) return nullptr;
-  TORCH_CHECK(alibi->scalar_type() == at::kFloat &&
-                  alibi->is_contiguous() && alibi->numel() == H,
-              "alibi slopes must be contiguous fp32 [H]");
-  return (const float*)alibi->const_data_ptr();
+// optional operand: is it there, and its data pointer or nullptr
+bool given(const c10::optional<at::Tensor>& t) {
+  return t.has_value() && t->defined();
 }
 
-// kv_lens: optional per-batch int32 [B] real KV lengths (continuous
-// batching decode); elements past a slot's length are masked
-static const int* kv_lens_ptr(const c10::optional<at::Tensor>& kv_lens,
-                              int64_t B) {
-  if (!kv_lens.has_value() || !kv_lens->defined()) return nullptr;
-  TORCH_CHECK(kv_lens->scalar_type() == at::kInt &&
-                  kv_lens->is_contiguous() && kv_lens->numel() == B,
-              "kv_lens must be contiguous int32 [B]");
-  return (const int*)kv_lens->const_data_ptr();
+const void* opt_ptr(const c10::optional<at::Tensor>& t) {
+  return given(t) ? t->const_data_ptr() : nullptr;
+}
+
+// The inputs every fused attention entry takes: q [B,H,S,D]; k and v
+// [B,H,Skv,D] (S != Skv is legal: ring attention, cached decode); optional
+// ALiBi slopes fp32 [H] and per-batch real KV lengths int32 [B] (continuous
+// batching decode; elements past a slot's length are masked).  head_dim is
+// a multiple of 16 up to max_D, up to 128 with slopes or lengths.
+void check_attn_inputs(const at::Tensor& q, const at::Tensor& k,
+                       const at::Tensor& v,
+                       const c10::optional<at::Tensor>& alibi,
+                       const c10::optional<at::Tensor>& kv_lens,
+                       int64_t max_D) {
+  check_bhsd(q, "q", -1, -1, -1, -1, q);
+  const int64_t B = q.size(0), H = q.size(1), D = q.size(3);
+  check_bhsd(k, "k", B, H, -1, D, q);
+  check_bhsd(v, "v", B, H, k.size(2), D, q);
+  TORCH_CHECK(D > 0 && D % 16 == 0 && D <= max_D,
+              "head_dim must be a multiple of 16 up to ", max_D, ", got ", D);
+  TORCH_CHECK(D <= 128 || !(given(alibi) || given(kv_lens)),
+              "alibi and kv_lens need head_dim <= 128, got ", D);
+  if (given(alibi)) check_vec(*alibi, "alibi", at::kFloat, H, q);
+  if (given(kv_lens)) check_vec(*kv_lens, "kv_lens", at::kInt, B, q);
 }
 
 at::Tensor attn_fwd_out(const at::Tensor& q, const at::Tensor& k,
@@ -457,20 +512,18 @@ at::Tensor attn_fwd_out(const at::Tensor& q, const at::Tensor& k,
                             c10::nullopt,
                         const c10::optional<at::Tensor>& kv_lens =
                             c10::nullopt) {
-  check_bf16_strided4(q, "q");
-  check_bf16_strided4(k, "k");
-  check_bf16_strided4(v, "v");
-  check_bf16_strided4(o, "o");
+  check_attn_inputs(q, k, v, alibi, kv_lens, 256);
   int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   int64_t Skv = k.size(2);
-  TORCH_CHECK(D % 16 == 0 && D <= 256, "head_dim must be <=256, mult of 16");
-  TORCH_CHECK(lse.is_contiguous() && lse.numel() == B * H * S);
+  check_bhsd(o, "o", B, H, S, D, q);
+  check_vec(lse, "lse", at::kFloat, B * H * S, q);
   const auto strides = bhs_strides(q, k, v, o);
   HIP_OK(launch_attn_fwd(q.const_data_ptr(), k.const_data_ptr(),
                          v.const_data_ptr(), o.mutable_data_ptr(),
                          (float*)lse.mutable_data_ptr(), B, H, S, Skv, D,
-                         (float)scale, causal ? 1 : 0, alibi_ptr(alibi, H),
-                         kv_lens_ptr(kv_lens, B), strides.data(),
+                         (float)scale, causal ? 1 : 0,
+                         (const float*)opt_ptr(alibi),
+                         (const int*)opt_ptr(kv_lens), strides.data(),
                          cur_stream()));
   return o;
 }
@@ -482,6 +535,8 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                      c10::nullopt,
                                  const c10::optional<at::Tensor>& kv_lens =
                                      c10::nullopt) {
+  // before the allocations; attn_fwd_out repeats it, which costs nothing
+  check_attn_inputs(q, k, v, alibi, kv_lens, 256);
   int64_t B = q.size(0), H = q.size(1), S = q.size(2);
   auto o = at::empty_like(q.contiguous());
   auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
@@ -575,16 +630,33 @@ std::vector<at::Tensor> attn_bwd_blocked(const at::Tensor& dout_, const at::Tens
 // two-kernel split).  All tensors are logical [B,H,S,D] views with
 // arbitrary B/H/S strides (contiguous D) — dq/dk/dv may be strided views
 // into a packed dqkv buffer.
+// dout, o [B,H,S,D] and the forward's lse, fp32 with B*H*S elements.
+// head_dim <= 128 as in the fused forward with the same operands, so no
+// o/lse pair exists for a wider head.
+void check_attn_bwd_inputs(const at::Tensor& dout, const at::Tensor& q,
+                           const at::Tensor& k, const at::Tensor& v,
+                           const at::Tensor& o, const at::Tensor& lse,
+                           const c10::optional<at::Tensor>& alibi) {
+  check_attn_inputs(q, k, v, alibi, c10::nullopt, 128);
+  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
+  check_bhsd(dout, "dout", B, H, S, D, q);
+  check_bhsd(o, "o", B, H, S, D, q);
+  check_typed(lse, "lse", at::kFloat, q);
+  TORCH_CHECK(lse.numel() == B * H * S, "lse must have ", B * H * S,
+              " elements, got ", lse.numel());
+}
+
 void attn_bwd_out(const at::Tensor& dout, const at::Tensor& q,
                   const at::Tensor& k, const at::Tensor& v,
                   const at::Tensor& o, const at::Tensor& lse, at::Tensor dq,
                   at::Tensor dk, at::Tensor dv, bool causal, double scale,
                   const c10::optional<at::Tensor>& alibi = c10::nullopt) {
-  check_bf16_strided4(q, "q");
-  check_bf16_strided4(dout, "dout");
-  check_bf16_strided4(dq, "dq");
+  check_attn_bwd_inputs(dout, q, k, v, o, lse, alibi);
   int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   int64_t Skv = k.size(2);
+  check_bhsd(dq, "dq", B, H, S, D, q);
+  check_bhsd(dk, "dk", B, H, Skv, D, q);
+  check_bhsd(dv, "dv", B, H, Skv, D, q);
   auto delta = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   auto lse_c = lse.contiguous();
   const auto strides = bhs_strides(q, k, v, dout, dq, dk, dv, o);
@@ -595,8 +667,9 @@ void attn_bwd_out(const at::Tensor& dout, const at::Tensor& q,
                          (float*)delta.mutable_data_ptr(),
                          dq.mutable_data_ptr(), dk.mutable_data_ptr(),
                          dv.mutable_data_ptr(), B, H, S, Skv, D,
-                         (float)scale, causal ? 1 : 0, alibi_ptr(alibi, H),
-                         strides.data(), cur_stream()));
+                         (float)scale, causal ? 1 : 0,
+                         (const float*)opt_ptr(alibi), strides.data(),
+                         cur_stream()));
 }
 
 std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
@@ -605,6 +678,8 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
                                  bool causal, double scale,
                                  const c10::optional<at::Tensor>& alibi =
                                      c10::nullopt) {
+  // before the allocations; attn_bwd_out repeats it, which costs nothing
+  check_attn_bwd_inputs(dout, q, k, v, o, lse, alibi);
   auto dq = at::empty_like(q.contiguous());
   auto dk = at::empty_like(k.contiguous());
   auto dv = at::empty_like(v.contiguous());
@@ -614,32 +689,15 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
 
 // ------------------------------ MoE routing ------------------------------
 
-void check_i32_vec(const at::Tensor& t, const char* name, int64_t n) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32");
-  TORCH_CHECK(t.is_contiguous() && t.numel() == n, name,
-              " must be contiguous with ", n, " elements");
-}
-
-// bf16 [rows, H] read or written with 16-byte accesses
-void check_moe_rows(const at::Tensor& t, const char* name) {
-  check_bf16_contig(t, name);
-  TORCH_CHECK(t.dim() == 2, name, " must be 2-D");
-  TORCH_CHECK(t.size(1) % 8 == 0 && t.size(1) >= 8, name,
-              ": H must be a positive multiple of 8");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.const_data_ptr()) % 16 == 0,
-              name, " must be 16-byte aligned");
-}
-
 constexpr int64_t kMoeMaxTokens = int64_t(1) << 30;
 
 // logits [N, E] bf16 -> (w1, w2, idx1, idx2, slot1, slot2, src, aux,
 // count1); every shape depends on (N, E, C) only and nothing is read back
 std::vector<at::Tensor> moe_route_fwd(const at::Tensor& logits,
                                       int64_t capacity) {
-  check_bf16_contig(logits, "logits");
+  auto [N, E] = check_rows(logits, "logits", 1, logits);
   TORCH_CHECK(logits.dim() == 2, "logits must be [N, E]");
-  const int64_t N = logits.size(0), E = logits.size(1), C = capacity;
+  const int64_t C = capacity;
   TORCH_CHECK(E >= 2 && E <= 128, "num_experts must be in [2, 128], got ", E);
   TORCH_CHECK(C >= 1, "capacity must be >= 1");
   TORCH_CHECK(C < (int64_t(1) << 31) / E, "E * capacity must be < 2^31");
@@ -683,19 +741,18 @@ at::Tensor moe_route_bwd(const at::Tensor& logits, const at::Tensor& idx1,
                          const at::Tensor& w2, const at::Tensor& count1,
                          const at::Tensor& dw1, const at::Tensor& dw2,
                          const at::Tensor& daux) {
-  check_bf16_contig(logits, "logits");
+  auto [N, E] = check_rows(logits, "logits", 1, logits);
   TORCH_CHECK(logits.dim() == 2, "logits must be [N, E]");
-  const int64_t N = logits.size(0), E = logits.size(1);
   TORCH_CHECK(E >= 2 && E <= 128, "num_experts must be in [2, 128], got ", E);
   TORCH_CHECK(N <= kMoeMaxTokens, "at most 2^30 tokens");
-  check_i32_vec(idx1, "idx1", N);
-  check_i32_vec(idx2, "idx2", N);
-  check_i32_vec(count1, "count1", E);
-  check_row_stats(w1, "w1", N);
-  check_row_stats(w2, "w2", N);
-  check_row_stats(dw1, "dw1", N);
-  check_row_stats(dw2, "dw2", N);
-  check_row_stats(daux, "daux", 1);
+  check_vec(idx1, "idx1", at::kInt, N, logits);
+  check_vec(idx2, "idx2", at::kInt, N, logits);
+  check_vec(count1, "count1", at::kInt, E, logits);
+  check_vec(w1, "w1", at::kFloat, N, logits);
+  check_vec(w2, "w2", at::kFloat, N, logits);
+  check_vec(dw1, "dw1", at::kFloat, N, logits);
+  check_vec(dw2, "dw2", at::kFloat, N, logits);
+  check_vec(daux, "daux", at::kFloat, 1, logits);
   auto dlogits = at::empty_like(logits);
   if (N == 0) return dlogits;
   HIP_OK(launch_moe_route_bwd(
@@ -714,18 +771,18 @@ at::Tensor moe_dispatch(const at::Tensor& x, const at::Tensor& src,
                         const c10::optional<at::Tensor>& slot1,
                         const c10::optional<at::Tensor>& w1,
                         const c10::optional<at::Tensor>& w2) {
-  check_moe_rows(x, "x");
-  const int64_t N = x.size(0), H = x.size(1), S = src.numel();
-  check_i32_vec(src, "src", S);
+  auto [N, H] = check_aligned_rows(x, "x", x);
+  const int64_t S = src.numel();
+  check_vec(src, "src", at::kInt, S, x);
   TORCH_CHECK(S < (int64_t(1) << 31), "E * capacity must be < 2^31");
   TORCH_CHECK(N <= kMoeMaxTokens, "at most 2^30 tokens");
   const bool scaled = slot1.has_value();
   TORCH_CHECK(w1.has_value() == scaled && w2.has_value() == scaled,
               "slot1, w1 and w2 go together");
   if (scaled) {
-    check_i32_vec(*slot1, "slot1", N);
-    check_row_stats(*w1, "w1", N);
-    check_row_stats(*w2, "w2", N);
+    check_vec(*slot1, "slot1", at::kInt, N, x);
+    check_vec(*w1, "w1", at::kFloat, N, x);
+    check_vec(*w2, "w2", at::kFloat, N, x);
   }
   auto out = at::empty({S, H}, x.options());
   if (S == 0) return out;
@@ -744,16 +801,16 @@ at::Tensor moe_combine(const at::Tensor& y,
                        const c10::optional<at::Tensor>& w1,
                        const c10::optional<at::Tensor>& w2,
                        const at::Tensor& slot1, const at::Tensor& slot2) {
-  check_moe_rows(y, "y");
-  const int64_t S = y.size(0), H = y.size(1), N = slot1.numel();
+  auto [S, H] = check_aligned_rows(y, "y", y);
+  const int64_t N = slot1.numel();
   TORCH_CHECK(S < (int64_t(1) << 31), "E * capacity must be < 2^31");
   TORCH_CHECK(N <= kMoeMaxTokens, "at most 2^30 tokens");
-  check_i32_vec(slot1, "slot1", N);
-  check_i32_vec(slot2, "slot2", N);
+  check_vec(slot1, "slot1", at::kInt, N, y);
+  check_vec(slot2, "slot2", at::kInt, N, y);
   TORCH_CHECK(w1.has_value() == w2.has_value(), "w1 and w2 go together");
   if (w1.has_value()) {
-    check_row_stats(*w1, "w1", N);
-    check_row_stats(*w2, "w2", N);
+    check_vec(*w1, "w1", at::kFloat, N, y);
+    check_vec(*w2, "w2", at::kFloat, N, y);
   }
   auto out = at::empty({N, H}, y.options());
   if (N == 0) return out;
@@ -771,14 +828,13 @@ std::vector<at::Tensor> moe_combine_dw(const at::Tensor& dout,
                                        const at::Tensor& y,
                                        const at::Tensor& slot1,
                                        const at::Tensor& slot2) {
-  check_moe_rows(dout, "dout");
-  check_moe_rows(y, "y");
-  const int64_t N = dout.size(0), H = dout.size(1), S = y.size(0);
-  TORCH_CHECK(y.size(1) == H, "dout and y must share H");
+  auto [N, H] = check_aligned_rows(dout, "dout", dout);
+  auto [S, Hy] = check_aligned_rows(y, "y", dout);
+  TORCH_CHECK(Hy == H, "dout and y must share H");
   TORCH_CHECK(S < (int64_t(1) << 31), "E * capacity must be < 2^31");
   TORCH_CHECK(N <= kMoeMaxTokens, "at most 2^30 tokens");
-  check_i32_vec(slot1, "slot1", N);
-  check_i32_vec(slot2, "slot2", N);
+  check_vec(slot1, "slot1", at::kInt, N, dout);
+  check_vec(slot2, "slot2", at::kInt, N, dout);
   auto f32 = dout.options().dtype(at::kFloat);
   auto dw1 = at::empty({N}, f32), dw2 = at::empty({N}, f32);
   if (N == 0) return {dw1, dw2};
@@ -790,8 +846,10 @@ std::vector<at::Tensor> moe_combine_dw(const at::Tensor& dout,
   return {dw1, dw2};
 }
 
+// both probes read one 512-element bf16 tile per operand
 at::Tensor mfma_probe(const at::Tensor& a, const at::Tensor& b) {
-  check_bf16_contig(a, "a");
+  check_vec(a, "a", at::kBFloat16, 512, a);
+  check_vec(b, "b", at::kBFloat16, 512, a);
   auto d = at::empty({16, 16}, a.options().dtype(at::kFloat));
   HIP_OK(launch_mfma_probe(a.const_data_ptr(), b.const_data_ptr(),
                            (float*)d.mutable_data_ptr(), cur_stream()));
@@ -799,7 +857,8 @@ at::Tensor mfma_probe(const at::Tensor& a, const at::Tensor& b) {
 }
 
 at::Tensor mfma_probe32(const at::Tensor& a, const at::Tensor& b) {
-  check_bf16_contig(a, "a");
+  check_vec(a, "a", at::kBFloat16, 512, a);
+  check_vec(b, "b", at::kBFloat16, 512, a);
   auto d = at::empty({32, 32}, a.options().dtype(at::kFloat));
   HIP_OK(launch_mfma_probe32(a.const_data_ptr(), b.const_data_ptr(),
                              (float*)d.mutable_data_ptr(), cur_stream()));
@@ -812,10 +871,9 @@ at::Tensor mfma_probe32(const at::Tensor& a, const at::Tensor& b) {
 std::vector<at::Tensor> fp8_quantize(const at::Tensor& x,
                                      const at::Tensor& scale, bool dual,
                                      bool e5m2) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
-              x.scalar_type() == at::kBFloat16, "x must be bf16 contiguous");
-  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat &&
-              scale.numel() == 1, "scale must be a device fp32 scalar");
+  // any shape: the single-layout kernel runs over the flat elements
+  check_vec(x, "x", at::kBFloat16, x.numel(), x);
+  check_vec(scale, "scale", at::kFloat, 1, x);
   auto qtype = e5m2 ? at::kFloat8_e5m2 : at::kFloat8_e4m3fn;
   auto amax = at::zeros({1}, x.options().dtype(at::kFloat));
   auto q = at::empty(x.sizes(), x.options().dtype(qtype));
@@ -840,12 +898,6 @@ std::vector<at::Tensor> fp8_quantize(const at::Tensor& x,
 
 // ---------------------- producers fused with quantize ----------------------
 
-// previous-step delayed scale: one fp32 element on the device
-void check_fp8_scale(const at::Tensor& scale) {
-  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat &&
-              scale.numel() == 1, "scale must be a device fp32 scalar");
-}
-
 // row tiles (64 rows) ride on grid.y, which holds at most 65535
 constexpr int64_t kFusedQuantMaxRows = int64_t(1) << 21;
 
@@ -855,14 +907,10 @@ constexpr int64_t kFusedQuantMaxRows = int64_t(1) << 21;
 std::vector<at::Tensor> bias_gelu_fp8(const at::Tensor& x,
                                       const at::Tensor& bias,
                                       const at::Tensor& scale) {
-  check_bf16_contig(x, "x");
-  TORCH_CHECK(x.dim() >= 1, "x must have a feature dimension");
-  int64_t F = x.size(-1);
-  TORCH_CHECK(F > 0 && F % 8 == 0, "F must be a positive multiple of 8");
-  int64_t N = x.numel() / F;
+  auto [N, F] = check_rows(x, "x", 8, x);
   TORCH_CHECK(N < kFusedQuantMaxRows, "at most 2^21 rows");
-  check_bf16_vec(bias, "bias", F);
-  check_fp8_scale(scale);
+  check_vec(bias, "bias", at::kBFloat16, F, x);
+  check_vec(scale, "scale", at::kFloat, 1, x);
   auto q8 = x.options().dtype(at::kFloat8_e4m3fn);
   auto amax = at::zeros({1}, x.options().dtype(at::kFloat));
   auto q = at::empty({N, F}, q8);
@@ -882,18 +930,14 @@ std::vector<at::Tensor> add_layer_norm_fp8(
     const at::Tensor& a, const c10::optional<at::Tensor>& b,
     const at::Tensor& w, const at::Tensor& bias, double eps,
     const at::Tensor& scale) {
-  check_bf16_contig(a, "a");
-  TORCH_CHECK(a.dim() >= 1, "a must have a feature dimension");
-  int64_t H = a.size(-1);
-  TORCH_CHECK(H > 0 && H % 8 == 0, "H must be a positive multiple of 8");
+  auto [N, H] = check_rows(a, "a", 8, a);
   // 16 rows of fp8 bytes are parked in 64 KB of LDS (FLN_MAX_H)
   TORCH_CHECK(H <= 4096, "add_layer_norm_fp8 handles H <= 4096, got ", H);
-  int64_t N = a.numel() / H;
   TORCH_CHECK(N < kFusedQuantMaxRows, "at most 2^21 rows");
-  if (b.has_value()) check_same_shape(*b, "b", a, "a");
-  check_bf16_vec(w, "w", H);
-  check_bf16_vec(bias, "bias", H);
-  check_fp8_scale(scale);
+  if (b.has_value()) check_like(*b, "b", a, "a");
+  check_vec(w, "w", at::kBFloat16, H, a);
+  check_vec(bias, "bias", at::kBFloat16, H, a);
+  check_vec(scale, "scale", at::kFloat, 1, a);
   auto f32 = a.options().dtype(at::kFloat);
   auto q8 = a.options().dtype(at::kFloat8_e4m3fn);
   auto h = at::empty_like(a);
