@@ -50,6 +50,29 @@ class GlobalConfig:
     skinny_gemm: str = field(
         default_factory=lambda: os.environ.get("ALPA_AMD_SKINNY",
                                                "auto"))
+    #: split-KV decode attention (ops/csrc/attention_decode.hip) for
+    #: single-token queries: ops.flash_attention at S_q == 1 outside
+    #: autograd and ops.flash_attention_varlen.  "auto" (default) means
+    #: on, everywhere inside the kernel's envelope (ops.decode_attn_ok):
+    #: tools/decode_attn_bench.py measured it against the path it replaces
+    #: (prefill kernel with kv_lens; blocked hipBLASLt path at head_dim
+    #: 256) on the OPT-13B/30B, BLOOM-7.1B and CodeGen-16B head shapes at
+    #: batch 1/8/32, lengths 128/512/2048, with and without 2048 keys of
+    #: capacity, and it was faster in all 60 rows, in all by more than the
+    #: round-to-round spread but one: 1.5-10x at batch 1, 2.2-3.4x on the
+    #: HBM-bound OPT/BLOOM rows, 1.2-1.5x on the HBM-bound CodeGen rows,
+    #: 3.7-9.3x at head_dim 128 with capacity beyond the slot length.  The exception
+    #: (CodeGen, batch 32, length 128 of 2048: 1.11x, spread 0.27) has no
+    #: other route: kv_lens at head_dim 256 exists in this kernel only.
+    #: Table in docs/BENCHMARK.md, "Decode attention".  End to end
+    #: (serve_bench, prompt 128): OPT-13B batch 32 12.50 -> 10.98 ms/token,
+    #: CodeGen-16B batch 8 14.02 -> 11.39, OPT-13B batch 1 unchanged;
+    #: OPT-13B batch 1 at prompt 1920: 12.30 -> 8.9.
+    #: ALPA_AMD_DECODE_ATTN=1 is the same as auto, =0 restores the prefill
+    #: kernel / blocked path.
+    decode_attention: str = field(
+        default_factory=lambda: os.environ.get("ALPA_AMD_DECODE_ATTN",
+                                               "auto"))
 
     #: compute dX with the bf16 MASTER weight instead of the fp8 wqt
     #: cache: halves the fp8 weight-cache footprint (the +30 GB dual

@@ -12,7 +12,9 @@ multi-tensor AdamW with global-norm gradient clipping (multi_tensor_sumsq
 feeds fused_adamw), and the sync-free top-2 MoE routing path: moe_top2_route (gate + capacity
 slots), moe_dispatch and moe_combine.  add_layer_norm_fp8 and bias_gelu_fp8
 are the LayerNorm and GeLU forwards with the fp8 quantize of ops/fp8.py
-folded in.
+folded in.  flash_attention_decode is the split-KV attention kernel for
+single-token queries, which flash_attention and flash_attention_varlen use
+for every decode step.
 
 Kernel-level contract mirrors the reference's compiled-HLO op inventory
 (GEMM+epilogue, attention, LayerNorm, fused Adam,
@@ -32,7 +34,8 @@ from ._backend import hip_ops, hip_ops_available, use_hip
 __all__ = [
     "layer_norm", "add_layer_norm", "bias_gelu", "add_layer_norm_fp8",
     "bias_gelu_fp8", "flash_attention",
-    "flash_attention_qkv", "softmax_cross_entropy",
+    "flash_attention_qkv", "flash_attention_decode", "decode_attn_ok",
+    "DECODE_ATTN_CHUNK", "softmax_cross_entropy",
     "softmax_cross_entropy_partial", "softmax_cross_entropy_combine",
     "softmax_cross_entropy_shard_bwd", "vocab_ce_fused_ok", "fused_adamw",
     "multi_tensor_sumsq",
@@ -252,8 +255,10 @@ class _FlashAttention(torch.autograd.Function):
                 # instantiation (single-buffered K/V, 512 threads) runs
                 # PREFILL 3.3-5x faster than the blocked hipBLASLt path
                 # (241 vs 70 TF at S=2048, tools/d256_probe.py); the
-                # blocked path keeps single-token DECODE (q rows << the
-                # kernel's 128-row block).  No alibi at D>128 (BLOOM
+                # blocked path keeps the few-row calls that reach this
+                # function (single-token decode goes to the split-KV
+                # kernel in flash_attention unless autograd records it or
+                # decode_attention is "0").  No alibi at D>128 (BLOOM
                 # heads are <=128).
                 assert alibi is None, "alibi requires head_dim <= 128"
                 if q.shape[2] >= 128 and q.shape[-1] <= 256:
@@ -301,7 +306,98 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     hand-written gfx950 kernel).  alibi_slopes [heads]
     (fp32) adds the BLOOM ALiBi bias inside the kernel.
     """
+    if q.shape[2] == 1 and not causal and _decode_attn_routed(q, k, v) and \
+            not (torch.is_grad_enabled() and
+                 (q.requires_grad or k.requires_grad or v.requires_grad)):
+        # single-token decode outside autograd: the split-KV kernel
+        if scale is None:
+            scale = 1.0 / math.sqrt(q.shape[-1])
+        return hip_ops().attn_decode(q, k, v, scale, alibi_slopes, None)[0]
     return _FlashAttention.apply(q, k, v, causal, scale, alibi_slopes)
+
+
+# keys per split-KV chunk by padded head dim; must match DecodeChunk in
+# csrc/attention_decode.hip (the extension's attn_decode_chunk reports it)
+_DECODE_ATTN_CHUNK = {64: 128, 128: 128, 256: 128}
+
+
+def DECODE_ATTN_CHUNK(head_dim: int) -> int:
+    """Keys per chunk of the split-KV decode kernel at this head_dim.  A
+    function of head_dim alone — never of the batch, the heads, the cache
+    length or the device — which is what makes a slot's output bits
+    independent of its neighbours and of the cache capacity."""
+    for dp in sorted(_DECODE_ATTN_CHUNK):
+        if head_dim <= dp:
+            return _DECODE_ATTN_CHUNK[dp]
+    raise ValueError(f"head_dim {head_dim} is above 256")
+
+
+def _rows_aligned16(t: torch.Tensor) -> bool:
+    return t.data_ptr() % 16 == 0 and all(
+        t.shape[i] <= 1 or t.stride(i) % 8 == 0 for i in range(3))
+
+
+def decode_attn_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
+    """Envelope of the split-KV decode attention kernel
+    (csrc/attention_decode.hip; the binding checks the same): bf16 on the
+    GPU, q [B, h, 1, d] and k, v [B, h, Skv, d] views with a contiguous
+    head dim, d a multiple of 16 up to 256, and every row 16-byte aligned
+    (aligned base, batch/head/seq strides multiples of 8 elements) for the
+    16-byte loads."""
+    for t in (q, k, v):
+        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
+                and t.stride(3) == 1):
+            return False
+    D = q.shape[3]
+    if q.shape[2] != 1 or D % 16 != 0 or not 16 <= D <= 256:
+        return False
+    if k.shape != v.shape or k.shape[:2] != q.shape[:2] or k.shape[3] != D \
+            or q.shape[0] * q.shape[1] > 65535:
+        return False
+    if not all(_rows_aligned16(t) for t in (q, k, v)):
+        return False
+    return use_hip(q)
+
+
+def _decode_attn_routed(q, k, v) -> bool:
+    """Do flash_attention / flash_attention_varlen send this single-token
+    call to the split-KV kernel?  global_config.decode_attention: "0" never,
+    "1" and "auto" whenever the call is inside the envelope (the rule and
+    its evidence are on the config field)."""
+    from ..global_env import global_config
+    if global_config.decode_attention in ("0", False):
+        return False
+    return decode_attn_ok(q, k, v)
+
+
+@torch.no_grad()
+def flash_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                           kv_lens: Optional[torch.Tensor] = None,
+                           scale: Optional[float] = None,
+                           alibi_slopes: Optional[torch.Tensor] = None
+                           ) -> torch.Tensor:
+    """Single-token decode attention: q [B, h, 1, d] attends, unmasked, to
+    the first kv_lens[b] (default all Skv) rows of k, v [B, h, Skv, d];
+    returns o [B, h, 1, d].  Inference only.
+
+    Inside decode_attn_ok this is the split-KV gfx950 kernel: the cache is
+    cut into chunks of DECODE_ATTN_CHUNK(d) keys, one workgroup each, and a
+    second launch merges them.  It reads strided views (a cache slice, the
+    q of a packed qkv projection) in place, never loads a row at or past a
+    slot's length, keeps P in fp32, and a slot's output bits depend only on
+    that slot's own q, visible k/v rows, length, d, scale and slope.  A slot
+    of length 0 gives o = 0.  kv_lens may live on the device, so the call
+    can be captured in a graph.  On CPU or outside the envelope it is
+    reference.attention_fwd."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    lens = None if kv_lens is None else kv_lens.to(dtype=torch.int32)
+    if decode_attn_ok(q, k, v):
+        return hip_ops().attn_decode(
+            q, k, v, scale, alibi_slopes,
+            None if lens is None else lens.contiguous())[0]
+    o, _ = ref.attention_fwd(q, k, v, False, scale, alibi_slopes, lens)
+    return o
 
 
 @torch.no_grad()
@@ -314,18 +410,24 @@ def flash_attention_varlen(q: torch.Tensor, k: torch.Tensor,
     slot b's queries attend to k[b, :, :kv_lens[b]].  Inference-only
     (no backward); the gfx950 kernel masks per element past each slot's
     length and never loads k or v there, so a stale NaN or Inf in a cache
-    tail is harmless.  A slot of length 0 gives o = 0."""
+    tail is harmless.  A slot of length 0 gives o = 0.  Single-token
+    queries go to the split-KV decode kernel (flash_attention_decode),
+    which also takes head_dim up to 256 and reads the cache view in
+    place."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     lens = kv_lens.to(dtype=torch.int32)
     if use_hip(q):
+        if q.shape[2] == 1 and _decode_attn_routed(q, k, v):
+            return hip_ops().attn_decode(q, k, v, scale, alibi_slopes,
+                                         lens.contiguous())[0]
         if q.shape[-1] > 128:
-            # the varlen (continuous-batching) template is instantiated
-            # for head_dim <= 128; CodeGen-class heads use per-request
-            # decode (unchanged from r1 — the Dp=256 instantiation
-            # covers the plain prefill/decode path only)
+            # the prefill kernel's varlen template is instantiated for
+            # head_dim <= 128: wider heads have the single-token decode
+            # kernel above only
             raise NotImplementedError(
-                "varlen attention requires head_dim <= 128")
+                "varlen attention with more than one query row, or with "
+                "the decode kernel off, requires head_dim <= 128")
         o, _ = hip_ops().attn_fwd(q.contiguous(), k.contiguous(),
                                   v.contiguous(), False, scale,
                                   alibi_slopes, lens.contiguous())

@@ -17,27 +17,12 @@
 //   A (16x32): m = lane&15, k = (lane>>4)*8 + j   (j = 0..7)
 //   B (32x16): n = lane&15, k = (lane>>4)*8 + j
 //   C/D      : n = lane&15, m = (lane>>4)*4 + reg (f32x4)
+#include "attn_strides.h"
 #include "common.h"
 #include "launchers.h"
 
 #define ATTN_BLOCK_K 64
 #define ATTN_FWD_THREADS 512
-
-// Strides are in elements; the innermost (D) dim must be contiguous.
-// Strided addressing lets the packed qkv layout [B, S, heads, 3*D] feed the
-// kernel directly — no permute/contiguous copies on the hot path.
-struct AttnStrides {
-  int64_t qb, qh, qs;  // q batch/head/seq strides
-  int64_t kb, kh, ks;
-  int64_t vb, vh, vs;
-  int64_t ob, oh, os;
-};
-
-// s: the launcher's 12-entry array, q(3) k(3) v(3) o(3)
-static AttnStrides attn_strides(const int64_t* s) {
-  return {s[0], s[1], s[2], s[3], s[4], s[5],
-          s[6], s[7], s[8], s[9], s[10], s[11]};
-}
 
 // Dp: head dim padded to the instantiated tile (64/96/128/256); AL: ALiBi
 // bias; VL: per-batch kv lengths (varlen decode).

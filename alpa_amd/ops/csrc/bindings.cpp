@@ -105,6 +105,20 @@ void check_bhsd(const at::Tensor& t, const char* name, int64_t B, int64_t H,
                 want[i], " in dimension ", i, ", got ", t.size(i));
 }
 
+// a [B, H, S, D] view (check_bhsd first) whose every row starts on a 16-byte
+// boundary, for kernels that read rows with 16-byte loads through arbitrary
+// strides: an aligned base and batch/head/seq strides that are multiples of
+// 8 elements.  The stride of a dimension of size 1 is never multiplied by a
+// non-zero index, so it is free.
+void check_rows_aligned16(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.const_data_ptr()) % 16 == 0, name,
+              " must be 16-byte aligned");
+  for (int i = 0; i < 3; ++i)
+    TORCH_CHECK(t.size(i) <= 1 || t.stride(i) % 8 == 0, name,
+                ": the stride of dimension ", i,
+                " must be a multiple of 8 elements, got ", t.stride(i));
+}
+
 // 2-D bf16 rows [N, W], W a positive multiple of 8, at a 16-byte-aligned
 // address: the vocab-shard CE and MoE entries, whose callers promise the
 // alignment.  Returns (N, W).
@@ -544,6 +558,51 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
   return {o, lse};
 }
 
+// Split-KV decode attention (attention_decode.hip): one query row per
+// (batch, head), non-causal over the first kv_lens[b] (or Skv) keys.
+// q [B,H,1,D], k and v [B,H,Skv,D] views as above, with 16-byte-aligned
+// rows; head_dim any multiple of 16 up to 256, with or without slopes and
+// lengths.  Returns (o [B,H,1,D] bf16, lse [B,H,1] fp32).  The workspace is
+// an ordinary allocation on the current stream, so the op can be captured.
+std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k,
+                                    const at::Tensor& v, double scale,
+                                    const c10::optional<at::Tensor>& alibi =
+                                        c10::nullopt,
+                                    const c10::optional<at::Tensor>& kv_lens =
+                                        c10::nullopt) {
+  check_bhsd(q, "q", -1, -1, -1, -1, q);
+  const int64_t B = q.size(0), H = q.size(1), D = q.size(3);
+  TORCH_CHECK(q.size(2) == 1, "q must hold one query row per head, got ",
+              q.size(2));
+  check_bhsd(k, "k", B, H, -1, D, q);
+  const int64_t Skv = k.size(2);
+  check_bhsd(v, "v", B, H, Skv, D, q);
+  TORCH_CHECK(D > 0 && D % 16 == 0 && D <= 256,
+              "head_dim must be a multiple of 16 up to 256, got ", D);
+  // (batch, head) pairs ride on grid.y
+  TORCH_CHECK(B * H <= 65535, "q: at most 65535 (batch, head) pairs, got ",
+              B * H);
+  if (given(alibi)) check_vec(*alibi, "alibi", at::kFloat, H, q);
+  if (given(kv_lens)) check_vec(*kv_lens, "kv_lens", at::kInt, B, q);
+  check_rows_aligned16(q, "q");
+  check_rows_aligned16(k, "k");
+  check_rows_aligned16(v, "v");
+  auto f32 = q.options().dtype(at::kFloat);
+  auto o = at::empty({B, H, 1, D}, q.options());
+  auto lse = at::empty({B, H, 1}, f32);
+  if (B * H == 0) return {o, lse};
+  auto ws = at::empty({attn_decode_workspace_floats(B, H, Skv, D)}, f32);
+  const auto strides = bhs_strides(q, k, v, o);
+  HIP_OK(launch_attn_decode(q.const_data_ptr(), k.const_data_ptr(),
+                            v.const_data_ptr(), o.mutable_data_ptr(),
+                            (float*)lse.mutable_data_ptr(),
+                            (float*)ws.mutable_data_ptr(), B, H, Skv, D,
+                            (float)scale, (const float*)opt_ptr(alibi),
+                            (const int*)opt_ptr(kv_lens), strides.data(),
+                            cur_stream()));
+  return {o, lse};
+}
+
 // Blocked attention forward for head_dim > 128 (the fused kernel tiles
 // head_dim in registers up to 128): q-block loop, scores via bf16
 // hipBLASLt GEMMs, fp32 softmax, never materializes more than one
@@ -970,7 +1029,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // max_grad_norm
   // 6: bias_gelu_fp8 and add_layer_norm_fp8 added
   // 7: cross_entropy_partial_fwd and cross_entropy_shard_bwd added
-  m.attr("ABI_VERSION") = 7;
+  // 8: attn_decode and attn_decode_chunk added
+  m.attr("ABI_VERSION") = 8;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)");
   m.def("add_layer_norm_fwd", &add_layer_norm_fwd,
@@ -1009,6 +1069,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("causal"), py::arg("scale"),
         py::arg("alibi") = py::none(), py::arg("kv_lens") = py::none());
+  m.def("attn_decode", &attn_decode,
+        "split-KV decode attention, one query row per head (gfx950)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+        py::arg("alibi") = py::none(), py::arg("kv_lens") = py::none());
+  m.def("attn_decode_chunk",
+        [](int64_t D) { return attn_decode_chunk(D); },
+        "keys per split-KV chunk of attn_decode at head_dim D");
   m.def("attn_fwd_blocked", &attn_fwd_blocked,
         "blocked fwd for head_dim > 128 (hipBLASLt scores)");
   m.def("attn_bwd", &attn_bwd, "flash attention bwd (gfx950 MFMA)",

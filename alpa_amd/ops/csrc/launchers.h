@@ -117,6 +117,21 @@ hipError_t launch_attn_bwd(const void* q, const void* k, const void* v,
                            int causal, const float* alibi,
                            const int64_t* strides, hipStream_t stream);
 
+// ---- attention_decode.hip ----
+// keys per split-KV chunk at head_dim D: a function of D alone
+int attn_decode_chunk(int64_t D);
+// fp32 elements of workspace the launch below needs (0 for a single chunk)
+int64_t attn_decode_workspace_floats(int64_t B, int64_t H, int64_t Skv,
+                                     int64_t D);
+// one query row per (batch, head), non-causal over the first kv_lens[b]
+// (or Skv) keys; strides as for launch_attn_fwd; q, k, v rows 16-byte
+// aligned; o [B,H,1,D] and lse [B*H] are written for every slot
+hipError_t launch_attn_decode(const void* q, const void* k, const void* v,
+                              void* o, float* lse, float* ws, int64_t B,
+                              int64_t H, int64_t Skv, int64_t D, float scale,
+                              const float* alibi, const int* kv_lens,
+                              const int64_t* strides, hipStream_t stream);
+
 // ---- moe_route.hip ----
 // top-2 + in-block ranks (left in slot1/slot2) + per-256-token-block
 // histograms and softmax column partials, all [ceil(N/256), E]

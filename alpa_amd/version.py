@@ -11,10 +11,9 @@ from __future__ import annotations
 
 __version__ = "0.1.0"
 
-#: minimum extension ABI this Python tree can drive (7:
-#: cross_entropy_partial_fwd and cross_entropy_shard_bwd, which the loss
-#: calls whenever the vocab is sharded over tp > 1)
-MIN_HIP_OPS_ABI = 7
+#: minimum extension ABI this Python tree can drive (8: attn_decode, which
+#: every single-token decode step calls)
+MIN_HIP_OPS_ABI = 8
 
 
 def check_hip_ops_version() -> int:
