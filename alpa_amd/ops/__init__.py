@@ -60,11 +60,13 @@ class _LayerNorm(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight, mean, rstd = ctx.saved_tensors
         if use_hip(x):
+            # dw and db leave the extension in the parameter dtype
             dx, dw, db = hip_ops().layer_norm_bwd(dy.contiguous(), x, weight,
-                                                  mean, rstd)
+                                                  mean, rstd, weight.dtype)
         else:
             dx, dw, db = ref.layer_norm_bwd(dy, x, weight, mean, rstd)
-        return dx, dw.to(weight.dtype), db.to(weight.dtype), None
+            dw, db = dw.to(weight.dtype), db.to(weight.dtype)
+        return dx, dw, db, None
 
 
 def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
@@ -97,14 +99,15 @@ class _AddLayerNorm(torch.autograd.Function):
         dy = dy.contiguous()
         dhc = dh.contiguous() if dh is not None else None
         if use_hip(h):
-            dx, dw, db = hip_ops().add_layer_norm_bwd(dy, dhc, h, weight,
-                                                      mean, rstd)
+            dx, dw, db = hip_ops().add_layer_norm_bwd(
+                dy, dhc, h, weight, mean, rstd, weight.dtype)
         else:
             dx, dw, db = ref.layer_norm_bwd(dy, h, weight, mean, rstd)
+            dw, db = dw.to(weight.dtype), db.to(weight.dtype)
             if dhc is not None:
                 dx = dx + dhc
         g2 = dx if ctx.has_delta else None
-        return dx, g2, dw.to(weight.dtype), db.to(weight.dtype), None
+        return dx, g2, dw, db, None
 
 
 def add_layer_norm(a: torch.Tensor, delta, weight: torch.Tensor,
@@ -130,10 +133,12 @@ class _BiasGelu(torch.autograd.Function):
     def backward(ctx, dy):
         x, bias = ctx.saved_tensors
         if use_hip(x):
-            dx, db = hip_ops().bias_gelu_bwd(dy.contiguous(), x, bias)
+            dx, db = hip_ops().bias_gelu_bwd(dy.contiguous(), x, bias,
+                                             bias.dtype)
         else:
             dx, db = ref.bias_gelu_bwd(dy, x, bias)
-        return dx, db.to(bias.dtype)
+            db = db.to(bias.dtype)
+        return dx, db
 
 
 def bias_gelu(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
@@ -179,6 +184,14 @@ def add_layer_norm_fp8(a: torch.Tensor, delta, weight: torch.Tensor,
     return ref.add_layer_norm_fp8(a, delta, weight, bias, eps, scale)
 
 
+def _colsum(g2: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """Column sum of bf16 rows [N, F] on the striped HIP kernels, reduced on
+    the device straight into `dtype` (a bias's)."""
+    if dtype in (torch.bfloat16, torch.float32):
+        return hip_ops().colsum_bf16(g2, dtype)
+    return hip_ops().colsum_bf16(g2).to(dtype)
+
+
 class _BiasAdd(torch.autograd.Function):
     """y = x + bias with the bias-grad column sum on the striped HIP
     kernel (torch's reduce path for broadcast-add backward cost ~8 ms
@@ -193,9 +206,8 @@ class _BiasAdd(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         if use_hip(g) and g.dtype == torch.bfloat16:
-            db = hip_ops().colsum_bf16(
-                g.contiguous().reshape(-1, ctx.feat))
-            db = db.to(ctx.bias_dtype)
+            db = _colsum(g.contiguous().reshape(-1, ctx.feat),
+                         ctx.bias_dtype)
         else:
             dims = tuple(range(g.dim() - 1))
             db = g.sum(dim=dims).to(ctx.bias_dtype)
@@ -230,7 +242,7 @@ class _LinearBias(torch.autograd.Function):
         dx = (g2 @ w).reshape(*g.shape[:-1], w.shape[1])
         dw = g2.t() @ x2
         if use_hip(g2) and g2.dtype == torch.bfloat16:
-            db = hip_ops().colsum_bf16(g2).to(ctx.bias_dtype)
+            db = _colsum(g2, ctx.bias_dtype)
         else:
             db = g2.sum(0).to(ctx.bias_dtype)
         return dx, dw, db

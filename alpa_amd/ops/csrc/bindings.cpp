@@ -132,16 +132,36 @@ std::pair<int64_t, int64_t> check_aligned_rows(const at::Tensor& t,
   return dims;
 }
 
-// Deterministic column-partial stripe count: enough (stripes x column
-// chunks) blocks to fill 256 CUs, bounded by the row count.  `chunk_cols` is
-// a tuning constant per kernel, not its block width: 256 for the LayerNorm
-// dw/db partial (whose blocks cover 1024 columns), 2048 for the bias-grad
-// partial, which has fewer column blocks and so wants more stripes.  The
-// result fixes the summation order of dw, db and dbias.
-int stripes_for(int64_t N, int64_t cols, int64_t chunk_cols) {
-  int64_t chunks = std::max<int64_t>(1, cols / chunk_cols);
+// Deterministic column-partial stripe count of the dbias kernels: enough
+// (stripes x 2048-column blocks) blocks to fill 256 CUs, bounded by the row
+// count.  The result fixes the summation order of dbias.  (LayerNorm's is
+// layer_norm_bwd_stripes, next to its kernels.)
+int stripes_for(int64_t N, int64_t cols) {
+  int64_t chunks = std::max<int64_t>(1, cols / 2048);
   int64_t p = std::max<int64_t>(64, 2048 / chunks);
   return (int)std::min<int64_t>({p, N, 512});
+}
+
+// the optional trailing out_dtype of the column reductions: fp32 (default)
+// or bf16
+at::ScalarType check_out_dtype(const c10::optional<at::ScalarType>& dtype) {
+  const at::ScalarType t = dtype.value_or(at::kFloat);
+  TORCH_CHECK(t == at::kFloat || t == at::kBFloat16,
+              "out_dtype must be fp32 or bf16, got ", dtype_name(t));
+  return t;
+}
+
+// out [F] (and out_b) = the stripe partials [P, F] summed over P on the
+// device, in a fixed order, written in out's dtype (check_out_dtype)
+void colsum_finalize(const at::Tensor& part, const at::Tensor* part_b,
+                     at::Tensor& out, at::Tensor* out_b) {
+  HIP_OK(launch_colsum_finalize(
+      (const float*)part.const_data_ptr(),
+      part_b != nullptr ? (const float*)part_b->const_data_ptr() : nullptr,
+      out.mutable_data_ptr(),
+      out_b != nullptr ? out_b->mutable_data_ptr() : nullptr,
+      (int)part.size(0), part.size(1),
+      out.scalar_type() == at::kBFloat16 ? 1 : 0, cur_stream()));
 }
 
 // ------------------------------- LayerNorm -------------------------------
@@ -164,48 +184,46 @@ std::vector<at::Tensor> layer_norm_fwd(const at::Tensor& x,
   return {y, mean, rstd};
 }
 
-// dw/db tail shared by both LayerNorm backwards (x is the normalized
-// input): striped column partials on the device, then the stripe-row
-// reduction through at::sum.
-std::pair<at::Tensor, at::Tensor> layer_norm_dwdb(const at::Tensor& dy,
-                                                  const at::Tensor& x,
-                                                  const at::Tensor& mean,
-                                                  const at::Tensor& rstd,
-                                                  int64_t N, int64_t H) {
-  auto f32 = x.options().dtype(at::kFloat);
-  auto dw = at::empty({H}, f32);
-  auto db = at::empty({H}, f32);
-  const int kStripes = stripes_for(N, H, 256);
-  auto dw_part = at::empty({kStripes, H}, f32);
-  auto db_part = at::empty({kStripes, H}, f32);
-  HIP_OK(launch_layer_norm_bwd_dwdb(
-      dy.const_data_ptr(), x.const_data_ptr(),
-      (const float*)mean.const_data_ptr(),
-      (const float*)rstd.const_data_ptr(),
-      (float*)dw_part.mutable_data_ptr(), (float*)db_part.mutable_data_ptr(),
-      N, H, kStripes, cur_stream()));
-  at::sum_out(dw, dw_part, {0});
-  at::sum_out(db, db_part, {0});
-  return {dw, db};
-}
-
-std::vector<at::Tensor> layer_norm_bwd(const at::Tensor& dy,
-                                       const at::Tensor& x,
-                                       const at::Tensor& w,
-                                       const at::Tensor& mean,
-                                       const at::Tensor& rstd) {
-  auto [N, H] = check_rows(x, "x", 8, x);
-  check_like(dy, "dy", x, "x");
+// Both LayerNorm backwards: `x` (named x_name in refusals) is the normalized
+// input, dh the residual gradient or null.  dx and the dw/db stripe partials
+// come from launch_layer_norm_bwd, dw and db from one finalize launch, in
+// out_dtype.
+std::vector<at::Tensor> layer_norm_bwd_common(
+    const at::Tensor& dy, const at::Tensor* dh, const at::Tensor& x,
+    const char* x_name, const at::Tensor& w, const at::Tensor& mean,
+    const at::Tensor& rstd, const c10::optional<at::ScalarType>& out_dtype) {
+  auto [N, H] = check_rows(x, x_name, 8, x);
+  check_like(dy, "dy", x, x_name);
+  if (dh != nullptr) check_like(*dh, "dh", x, x_name);
   check_vec(w, "w", at::kBFloat16, H, x);
   check_vec(mean, "mean", at::kFloat, N, x);
   check_vec(rstd, "rstd", at::kFloat, N, x);
+  const at::ScalarType odt = check_out_dtype(out_dtype);
+  auto f32 = x.options().dtype(at::kFloat);
   auto dx = at::empty_like(x);
-  HIP_OK(launch_layer_norm_bwd_dx(
-      dy.const_data_ptr(), nullptr, x.const_data_ptr(), w.const_data_ptr(),
-      (const float*)mean.const_data_ptr(), (const float*)rstd.const_data_ptr(),
-      dx.mutable_data_ptr(), N, H, cur_stream()));
-  auto [dw, db] = layer_norm_dwdb(dy, x, mean, rstd, N, H);
+  auto dw = at::empty({H}, x.options().dtype(odt));
+  auto db = at::empty({H}, x.options().dtype(odt));
+  const int kStripes = layer_norm_bwd_stripes(N, H);
+  auto dw_part = at::empty({kStripes, H}, f32);
+  auto db_part = at::empty({kStripes, H}, f32);
+  if (N > 0) {
+    HIP_OK(launch_layer_norm_bwd(
+        dy.const_data_ptr(), dh != nullptr ? dh->const_data_ptr() : nullptr,
+        x.const_data_ptr(), w.const_data_ptr(),
+        (const float*)mean.const_data_ptr(),
+        (const float*)rstd.const_data_ptr(), dx.mutable_data_ptr(),
+        (float*)dw_part.mutable_data_ptr(),
+        (float*)db_part.mutable_data_ptr(), N, H, cur_stream()));
+  }
+  colsum_finalize(dw_part, &db_part, dw, &db);
   return {dx, dw, db};
+}
+
+std::vector<at::Tensor> layer_norm_bwd(
+    const at::Tensor& dy, const at::Tensor& x, const at::Tensor& w,
+    const at::Tensor& mean, const at::Tensor& rstd,
+    const c10::optional<at::ScalarType>& out_dtype) {
+  return layer_norm_bwd_common(dy, nullptr, x, "x", w, mean, rstd, out_dtype);
 }
 
 // --------------------------- Add + LayerNorm -----------------------------
@@ -236,22 +254,9 @@ std::vector<at::Tensor> add_layer_norm_fwd(const at::Tensor& a,
 std::vector<at::Tensor> add_layer_norm_bwd(
     const at::Tensor& dy, const c10::optional<at::Tensor>& dh,
     const at::Tensor& h, const at::Tensor& w, const at::Tensor& mean,
-    const at::Tensor& rstd) {
-  auto [N, H] = check_rows(h, "h", 8, h);
-  check_like(dy, "dy", h, "h");
-  if (dh.has_value()) check_like(*dh, "dh", h, "h");
-  check_vec(w, "w", at::kBFloat16, H, h);
-  check_vec(mean, "mean", at::kFloat, N, h);
-  check_vec(rstd, "rstd", at::kFloat, N, h);
-  auto dx = at::empty_like(h);
-  const void* dhp = dh.has_value() ? dh->const_data_ptr() : nullptr;
-  HIP_OK(launch_layer_norm_bwd_dx(
-      dy.const_data_ptr(), dhp, h.const_data_ptr(), w.const_data_ptr(),
-      (const float*)mean.const_data_ptr(),
-      (const float*)rstd.const_data_ptr(), dx.mutable_data_ptr(), N, H,
-      cur_stream()));
-  auto [dw, db] = layer_norm_dwdb(dy, h, mean, rstd, N, H);
-  return {dx, dw, db};
+    const at::Tensor& rstd, const c10::optional<at::ScalarType>& out_dtype) {
+  return layer_norm_bwd_common(dy, dh.has_value() ? &*dh : nullptr, h, "h", w,
+                               mean, rstd, out_dtype);
 }
 
 // ------------------------------- BiasGelu --------------------------------
@@ -265,39 +270,45 @@ at::Tensor bias_gelu_fwd(const at::Tensor& x, const at::Tensor& bias) {
   return y;
 }
 
-std::vector<at::Tensor> bias_gelu_bwd(const at::Tensor& dy,
-                                      const at::Tensor& x,
-                                      const at::Tensor& bias) {
+// (dx, dbias): dbias is the column sum of the returned (rounded) dx
+std::vector<at::Tensor> bias_gelu_bwd(
+    const at::Tensor& dy, const at::Tensor& x, const at::Tensor& bias,
+    const c10::optional<at::ScalarType>& out_dtype) {
   auto [N, F] = check_rows(x, "x", 8, x);
   check_like(dy, "dy", x, "x");
   check_vec(bias, "bias", at::kBFloat16, F, x);
+  const at::ScalarType odt = check_out_dtype(out_dtype);
   auto dx = at::empty_like(x);
-  auto f32 = x.options().dtype(at::kFloat);
-  const int kStripes = stripes_for(N, F, 2048);
-  auto db = at::empty({F}, f32);
-  auto db_part = at::empty({kStripes, F}, f32);
-  HIP_OK(launch_bias_gelu_bwd(dy.const_data_ptr(), x.const_data_ptr(),
-                              bias.const_data_ptr(), dx.mutable_data_ptr(),
-                              (float*)db_part.mutable_data_ptr(), N, F,
-                              kStripes, cur_stream()));
-  at::sum_out(db, db_part, {0});
+  const int kStripes = stripes_for(N, F);
+  auto db = at::empty({F}, x.options().dtype(odt));
+  auto db_part = at::empty({kStripes, F}, x.options().dtype(at::kFloat));
+  if (N > 0) {
+    HIP_OK(launch_bias_gelu_bwd(dy.const_data_ptr(), x.const_data_ptr(),
+                                bias.const_data_ptr(), dx.mutable_data_ptr(),
+                                (float*)db_part.mutable_data_ptr(), N, F,
+                                kStripes, cur_stream()));
+  }
+  colsum_finalize(db_part, nullptr, db, nullptr);
   return {dx, db};
 }
 
-// column sum of a bf16 [N, F] tensor -> fp32 [F] (striped partials +
-// at::sum): the bias-gradient reduction for plain +bias layers (the
+// column sum of a bf16 [N, F] tensor -> [F] in out_dtype (striped partials +
+// finalize): the bias-gradient reduction for plain +bias layers (the
 // at::native reduce path cost ~8 ms/step in the r2 profile)
-at::Tensor colsum_bf16(const at::Tensor& t) {
-  // any positive width: the kernel has a scalar tail
+at::Tensor colsum_bf16(const at::Tensor& t,
+                       const c10::optional<at::ScalarType>& out_dtype) {
+  // any positive width: the kernels have a scalar tail
   auto [N, F] = check_rows(t, "t", 1, t);
-  auto f32 = t.options().dtype(at::kFloat);
-  const int kStripes = stripes_for(N, F, 2048);
-  auto part = at::empty({kStripes, F}, f32);
-  auto out = at::empty({F}, f32);
-  HIP_OK(launch_colsum_partial(t.const_data_ptr(),
-                               (float*)part.mutable_data_ptr(), N, F,
-                               kStripes, cur_stream()));
-  at::sum_out(out, part, {0});
+  const at::ScalarType odt = check_out_dtype(out_dtype);
+  const int kStripes = stripes_for(N, F);
+  auto part = at::empty({kStripes, F}, t.options().dtype(at::kFloat));
+  auto out = at::empty({F}, t.options().dtype(odt));
+  if (N > 0) {
+    HIP_OK(launch_colsum_partial(t.const_data_ptr(),
+                                 (float*)part.mutable_data_ptr(), N, F,
+                                 kStripes, cur_stream()));
+  }
+  colsum_finalize(part, nullptr, out, nullptr);
   return out;
 }
 
@@ -1030,16 +1041,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // 6: bias_gelu_fp8 and add_layer_norm_fp8 added
   // 7: cross_entropy_partial_fwd and cross_entropy_shard_bwd added
   // 8: attn_decode and attn_decode_chunk added
-  m.attr("ABI_VERSION") = 8;
+  // 9: layer_norm_bwd, add_layer_norm_bwd, bias_gelu_bwd and colsum_bf16
+  // take an optional out_dtype (fp32 or bf16) for the vectors they reduce
+  m.attr("ABI_VERSION") = 9;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
-  m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)");
+  m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)",
+        py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),
+        py::arg("rstd"), py::arg("out_dtype") = py::none());
   m.def("add_layer_norm_fwd", &add_layer_norm_fwd,
         "fused residual-add + LayerNorm fwd (gfx950)");
   m.def("add_layer_norm_bwd", &add_layer_norm_bwd,
-        "fused residual-add + LayerNorm bwd (gfx950)");
+        "fused residual-add + LayerNorm bwd (gfx950)", py::arg("dy"),
+        py::arg("dh"), py::arg("h"), py::arg("w"), py::arg("mean"),
+        py::arg("rstd"), py::arg("out_dtype") = py::none());
   m.def("bias_gelu_fwd", &bias_gelu_fwd, "bias+GeLU forward (gfx950)");
-  m.def("bias_gelu_bwd", &bias_gelu_bwd, "bias+GeLU backward (gfx950)");
-  m.def("colsum_bf16", &colsum_bf16, "striped column sum (gfx950)");
+  m.def("bias_gelu_bwd", &bias_gelu_bwd, "bias+GeLU backward (gfx950)",
+        py::arg("dy"), py::arg("x"), py::arg("bias"),
+        py::arg("out_dtype") = py::none());
+  m.def("colsum_bf16", &colsum_bf16, "striped column sum (gfx950)",
+        py::arg("t"), py::arg("out_dtype") = py::none());
   m.def("skinny_gemm", &skinny_gemm,
         "decode GEMV over packed weights (gfx950)");
   m.def("adamw_step_raw", &adamw_step_raw, "multi-tensor AdamW (gfx950)",

@@ -16,18 +16,16 @@ extern "C" {
 hipError_t launch_layer_norm_fwd(const void* x, const void* w, const void* b,
                                  void* y, float* mean, float* rstd, int64_t N,
                                  int64_t H, float eps, hipStream_t stream);
-// dh: residual gradient added to dx, or null
-hipError_t launch_layer_norm_bwd_dx(const void* dy, const void* dh,
-                                    const void* x, const void* w,
-                                    const float* mean, const float* rstd,
-                                    void* dx, int64_t N, int64_t H,
-                                    hipStream_t stream);
-// dw_part/db_part [P, H]: the caller sums them over P
-hipError_t launch_layer_norm_bwd_dwdb(const void* dy, const void* x,
-                                      const float* mean, const float* rstd,
-                                      float* dw_part, float* db_part,
-                                      int64_t N, int64_t H, int P,
-                                      hipStream_t stream);
+// stripe count P of the backward below: a function of (N, H) alone
+int layer_norm_bwd_stripes(int64_t N, int64_t H);
+// dx and the dw/db stripe partials [P, H], which launch_colsum_finalize sums;
+// one fused kernel for H <= 4096, the dx + dw/db-partial pair for wider rows.
+// dh: residual gradient added to dx, or null.  N >= 1.
+hipError_t launch_layer_norm_bwd(const void* dy, const void* dh,
+                                 const void* x, const void* w,
+                                 const float* mean, const float* rstd,
+                                 void* dx, float* dw_part, float* db_part,
+                                 int64_t N, int64_t H, hipStream_t stream);
 hipError_t launch_add_layer_norm_fwd(const void* a, const void* b,
                                      const void* w, const void* bias,
                                      void* h, void* y, float* mean,
@@ -37,12 +35,19 @@ hipError_t launch_add_layer_norm_fwd(const void* a, const void* b,
 // ---- bias_gelu.hip ----
 hipError_t launch_bias_gelu_fwd(const void* x, const void* bias, void* y,
                                 int64_t N, int64_t F, hipStream_t stream);
+// dx and the dbias stripe partials db_part [P, F], in one kernel
 hipError_t launch_bias_gelu_bwd(const void* dy, const void* x,
                                 const void* bias, void* dx, float* db_part,
                                 int64_t N, int64_t F, int P,
                                 hipStream_t stream);
 hipError_t launch_colsum_partial(const void* t, float* part, int64_t N,
                                  int64_t F, int P, hipStream_t stream);
+// out_a[c] = sum over p of part_a[p, c], fixed order, fp32 or (out_bf16)
+// bf16 rounded to nearest even; likewise part_b -> out_b in the same launch
+// unless part_b is null.  P >= 0, any F >= 1.
+hipError_t launch_colsum_finalize(const float* part_a, const float* part_b,
+                                  void* out_a, void* out_b, int P, int64_t F,
+                                  int out_bf16, hipStream_t stream);
 
 // ---- adamw.hip ----
 hipError_t launch_adamw(const void* descs_dev, const void* chunks_dev,

@@ -171,7 +171,7 @@ def _linear_bwd(ctx, xsaved, wb, sx, ws, dy):
         dw = dy2.t() @ xsaved     # exact bf16 weight grad
     db = None
     if ctx.has_bias:
-        db = hip_ops().colsum_bf16(dy2).to(dy.dtype)
+        db = hip_ops().colsum_bf16(dy2, dy.dtype)
     return dx, dw, db
 
 
@@ -269,15 +269,14 @@ class _Fp8LnLinear(torch.autograd.Function):
             # as _AddLayerNorm.backward
             dh = grads[0].contiguous() if grads[0] is not None else None
             dx, dlw, dlb = hip_ops().add_layer_norm_bwd(
-                dy, dh, h, ln_weight, mean, rstd)
+                dy, dh, h, ln_weight, mean, rstd, ln_weight.dtype)
             g2 = dx
         else:
             # as _LayerNorm.backward: autograd adds the residual grad
             dx, dlw, dlb = hip_ops().layer_norm_bwd(dy, h, ln_weight, mean,
-                                                    rstd)
+                                                    rstd, ln_weight.dtype)
             g2 = None
-        return (dx, g2, dlw.to(ln_weight.dtype), dlb.to(ln_weight.dtype),
-                None, dw, db, None)
+        return (dx, g2, dlw, dlb, None, dw, db, None)
 
 
 def fp8_ln_linear(res: torch.Tensor, delta: Optional[torch.Tensor],
@@ -323,9 +322,9 @@ class _Fp8GeluLinear(torch.autograd.Function):
         *lin, x2, gelu_bias = ctx.saved_tensors
         dy, dw, _ = _linear_bwd(ctx, *lin, dout)
         # as _BiasGelu.backward
-        dx, db = hip_ops().bias_gelu_bwd(dy.contiguous(), x2, gelu_bias)
-        return (dx.reshape(*dout.shape[:-1], x2.shape[-1]),
-                db.to(gelu_bias.dtype), dw, None)
+        dx, db = hip_ops().bias_gelu_bwd(dy.contiguous(), x2, gelu_bias,
+                                         gelu_bias.dtype)
+        return (dx.reshape(*dout.shape[:-1], x2.shape[-1]), db, dw, None)
 
 
 def fp8_gelu_linear(x_pre: torch.Tensor, gelu_bias: torch.Tensor,

@@ -11,9 +11,10 @@ from __future__ import annotations
 
 __version__ = "0.1.0"
 
-#: minimum extension ABI this Python tree can drive (8: attn_decode, which
-#: every single-token decode step calls)
-MIN_HIP_OPS_ABI = 8
+#: minimum extension ABI this Python tree can drive (9: the backward entries
+#: of LayerNorm, bias+GeLU and the bias column sum take the out_dtype that
+#: every autograd function passes)
+MIN_HIP_OPS_ABI = 9
 
 
 def check_hip_ops_version() -> int:
