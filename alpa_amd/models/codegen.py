@@ -15,15 +15,9 @@ from dataclasses import dataclass
 from typing import Optional
 
 import torch
-import torch.nn as nn
 
-from .. import ops
 from ..mesh import DeviceMesh
-from ..parallel.layers import (ColumnParallelLinear, RowParallelLinear,
-                               VocabParallelEmbedding)
-from .generation import GenerationMixin
-from .gpt import LayerNorm
-from .opt import KVCache
+from .decoder import CachedDecoder, DecoderBlock, KVCache  # noqa: F401
 
 
 @dataclass
@@ -80,111 +74,41 @@ def apply_rotary(x: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor,
     return torch.cat([rot.flatten(-2), x[..., rotary_dim:]], dim=-1)
 
 
-class CodeGenBlock(nn.Module):
+class CodeGenBlock(DecoderBlock):
     """Parallel-residual block: x + attn(ln x) + mlp(ln x) (GPT-J)."""
 
     def __init__(self, cfg: CodeGenConfig, mesh, axis, dtype, device, idx,
                  init_seed):
-        super().__init__()
-        tp = mesh.axis_size(axis) if mesh is not None else 1
-        self.heads_per_rank = cfg.num_heads // tp
-        self.head_dim = cfg.head_dim
-        self.rotary_dim = cfg.rotary_dim
-        self.ln = LayerNorm(cfg.hidden_size, cfg.layernorm_eps, dtype,
-                            device)
-        self.qkv = ColumnParallelLinear(cfg.hidden_size, 3 * cfg.hidden_size,
-                                        mesh, axis, dtype=dtype,
-                                        device=device, init_seed=init_seed,
-                                        init_tag=f"b{idx}.qkv")
-        self.out = RowParallelLinear(cfg.hidden_size, cfg.hidden_size, mesh,
-                                     axis, dtype=dtype, device=device,
-                                     init_seed=init_seed,
-                                     init_tag=f"b{idx}.out")
-        self.fc1 = ColumnParallelLinear(cfg.hidden_size,
-                                        cfg.ffn_mult * cfg.hidden_size,
-                                        mesh, axis, gelu=True, dtype=dtype,
-                                        device=device, init_seed=init_seed,
-                                        init_tag=f"b{idx}.fc1")
-        self.fc2 = RowParallelLinear(cfg.ffn_mult * cfg.hidden_size,
-                                     cfg.hidden_size, mesh, axis,
-                                     dtype=dtype, device=device,
-                                     init_seed=init_seed,
-                                     init_tag=f"b{idx}.fc2")
-
-    def _attn(self, y, cache_k, cache_v, start_pos: int, sin, cos):
-        B, S, _ = y.shape
-        h, d = self.heads_per_rank, self.head_dim
-        qkv = self.qkv(y).view(B, S, h, 3, d)
-        q = qkv[:, :, :, 0].permute(0, 2, 1, 3)
-        k = qkv[:, :, :, 1].permute(0, 2, 1, 3)
-        v = qkv[:, :, :, 2].permute(0, 2, 1, 3)
-        q = apply_rotary(q, sin, cos, start_pos, self.rotary_dim)
-        k = apply_rotary(k, sin, cos, start_pos, self.rotary_dim)
-        cache_k[:, :, start_pos:start_pos + S] = k
-        cache_v[:, :, start_pos:start_pos + S] = v
-        total = start_pos + S
-        kc = cache_k[:, :, :total]
-        vc = cache_v[:, :, :total]
-        o = ops.flash_attention(q.contiguous(), kc, vc,
-                                causal=(S == total and S > 1))
-        return self.out(o.permute(0, 2, 1, 3).reshape(B, S, h * d))
-
-    def forward(self, x, cache_k, cache_v, start_pos: int, sin, cos):
-        y = self.ln(x)
-        return x + self._attn(y, cache_k, cache_v, start_pos, sin, cos) + \
-            self.fc2(self.fc1(y))
+        super().__init__(cfg, mesh, axis, dtype, device, idx, init_seed,
+                         gelu=True, parallel=True)
 
 
-class CodeGenModel(nn.Module, GenerationMixin):
+class CodeGenModel(CachedDecoder):
     """TP-sharded CodeGen decoder with KV-cache generation."""
+
+    block_cls = CodeGenBlock
 
     def __init__(self, cfg: CodeGenConfig, mesh: Optional[DeviceMesh] = None,
                  axis: int = 1, dtype=torch.float32, device=None,
                  init_seed: int = 0):
-        super().__init__()
-        self.cfg = cfg
-        assert cfg.head_dim <= 256, (
-            f"head_dim {cfg.head_dim} > 256 unsupported; dims in "
-            "(128, 256] use the blocked hipBLASLt attention path")
-        self.mesh, self.axis = mesh, axis
-        tp = mesh.axis_size(axis) if mesh is not None else 1
-        self.heads_per_rank = cfg.num_heads // tp
-        self.wte = VocabParallelEmbedding(cfg.vocab_size, cfg.hidden_size,
-                                          mesh, axis, dtype=dtype,
-                                          device=device,
-                                          init_seed=init_seed,
-                                          init_tag="wte")
-        self.blocks = nn.ModuleList([
-            CodeGenBlock(cfg, mesh, axis, dtype, device, i, init_seed)
-            for i in range(cfg.num_layers)
-        ])
-        self.ln_f = LayerNorm(cfg.hidden_size, cfg.layernorm_eps, dtype,
-                              device)
-        self.lm_head = ColumnParallelLinear(cfg.hidden_size, cfg.vocab_size,
-                                            mesh, axis, bias=False,
-                                            dtype=dtype, device=device,
-                                            init_seed=init_seed,
-                                            init_tag="lm_head")
-        self.lm_head._fp8_exclude = True  # logits GEMM stays bf16
+        super().__init__(cfg, mesh, axis, dtype, device, init_seed)
         sin, cos = rotary_tables(cfg.rotary_dim, cfg.max_seq_len, dtype,
                                  device)
         self.register_buffer("rot_sin", sin, persistent=False)
         self.register_buffer("rot_cos", cos, persistent=False)
-        self.dtype = dtype
-        self.device_ = device
 
-    def new_cache(self, batch: int) -> KVCache:
-        return KVCache(self.cfg, self.cfg.num_layers, batch,
-                       self.heads_per_rank, self.dtype, self.device_)
+    def _embed(self, ids, pos):
+        return self.wte(ids)
 
-    def forward_step(self, ids: torch.Tensor, cache: KVCache
-                     ) -> torch.Tensor:
-        B, S = ids.shape
-        pos = cache.length
-        assert pos == 0 or S == 1, "chunked decode with history unsupported"
-        x = self.wte(ids)
-        for i, blk in enumerate(self.blocks):
-            x = blk(x, cache.k[i], cache.v[i], pos, self.rot_sin,
-                    self.rot_cos)
-        cache.length += S
-        return self.lm_head(self.ln_f(x[:, -1:]))[:, 0]
+    def _rotate(self, x, pos):
+        if not isinstance(pos, int):
+            raise NotImplementedError(
+                "CodeGen rotary takes one int position for the whole batch; "
+                "per-slot positions (forward_decode, continuous batching) "
+                "are not implemented")
+        return apply_rotary(x, self.rot_sin, self.rot_cos, pos,
+                            self.cfg.rotary_dim)
+
+    def _attn_args(self):
+        return {"rotate": self._rotate}
+

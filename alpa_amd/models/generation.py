@@ -10,7 +10,9 @@ Capability analog of the reference's huggingface GenerationMixin adapter
   - ``self.new_cache(batch)``           preallocated KV cache
   - ``self.forward_step(ids, cache)``   prefill/decode -> last logits
 
-Used by OPTModel and CodeGenModel.
+``models/decoder.py`` CachedDecoder provides all four (with ``KVCache``,
+per-slot ``forward_decode`` and the hipGraph decode loop) for OPTModel,
+BloomModel and CodeGenModel.
 """
 from __future__ import annotations
 

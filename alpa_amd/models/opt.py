@@ -11,20 +11,15 @@ BASELINE config 5: OPT-30B auto-sharded TP across 8x MI355X.
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import Optional
 
 import torch
-import torch.distributed as dist
 import torch.nn as nn
 
-from .. import ops
-from ..mesh import DeviceMesh, is_distributed
-from ..parallel.layers import (ColumnParallelLinear, RowParallelLinear,
-                               VocabParallelEmbedding, reduce_from_tp)
-from .generation import GenerationMixin
-from .gpt import LayerNorm
+from ..mesh import DeviceMesh
+from ..parallel.layers import tag_seed
+from .decoder import CachedDecoder, DecoderBlock, KVCache  # noqa: F401
 
 
 @dataclass
@@ -61,314 +56,41 @@ def opt_config(name: str, max_seq_len: int = 2048) -> OPTConfig:
                      max_seq_len=max_seq_len)
 
 
-class KVCache:
-    """Per-layer preallocated cache [B, heads/tp, max_len, d] (analog of
-    the reference's cache-as-DistributedArrays kept on mesh,
-    wrapper.py:356-371)."""
-
-    def __init__(self, cfg: OPTConfig, num_layers: int, batch: int,
-                 heads_per_rank: int, dtype, device,
-                 max_len: Optional[int] = None):
-        d = cfg.head_dim
-        max_len = max_len or cfg.max_seq_len
-        self.k = [torch.zeros(batch, heads_per_rank, max_len, d,
-                              dtype=dtype, device=device)
-                  for _ in range(num_layers)]
-        self.v = [torch.zeros(batch, heads_per_rank, max_len, d,
-                              dtype=dtype, device=device)
-                  for _ in range(num_layers)]
-        self.length = 0
-
-    def reorder(self, beam_idx: torch.Tensor):
-        """Beam-search cache reorder (reference index-select executables,
-        mesh_executable.py:1168)."""
-        for i in range(len(self.k)):
-            self.k[i] = self.k[i].index_select(0, beam_idx)
-            self.v[i] = self.v[i].index_select(0, beam_idx)
 
 
-class OPTBlock(nn.Module):
+class OPTBlock(DecoderBlock):
+    """Sequential ln1/ln2 residuals, relu MLP."""
 
     def __init__(self, cfg: OPTConfig, mesh, axis, dtype, device, idx,
                  init_seed):
-        super().__init__()
-        tp = mesh.axis_size(axis) if mesh is not None else 1
-        self.heads_per_rank = cfg.num_heads // tp
-        self.head_dim = cfg.head_dim
-        self.ln1 = LayerNorm(cfg.hidden_size, cfg.layernorm_eps, dtype,
-                             device)
-        self.qkv = ColumnParallelLinear(cfg.hidden_size, 3 * cfg.hidden_size,
-                                        mesh, axis, dtype=dtype,
-                                        device=device, init_seed=init_seed,
-                                        init_tag=f"b{idx}.qkv")
-        self.out = RowParallelLinear(cfg.hidden_size, cfg.hidden_size, mesh,
-                                     axis, dtype=dtype, device=device,
-                                     init_seed=init_seed,
-                                     init_tag=f"b{idx}.out")
-        self.ln2 = LayerNorm(cfg.hidden_size, cfg.layernorm_eps, dtype,
-                             device)
-        self.fc1 = ColumnParallelLinear(cfg.hidden_size,
-                                        cfg.ffn_mult * cfg.hidden_size, mesh,
-                                        axis, dtype=dtype, device=device,
-                                        init_seed=init_seed,
-                                        init_tag=f"b{idx}.fc1")
-        self.fc2 = RowParallelLinear(cfg.ffn_mult * cfg.hidden_size,
-                                     cfg.hidden_size, mesh, axis,
-                                     dtype=dtype, device=device,
-                                     init_seed=init_seed,
-                                     init_tag=f"b{idx}.fc2")
-
-    def _attn(self, x, cache_k, cache_v, start_pos: int):
-        B, S, _ = x.shape
-        h, d = self.heads_per_rank, self.head_dim
-        qkv = self.qkv(x).view(B, S, h, 3, d)
-        q = qkv[:, :, :, 0].permute(0, 2, 1, 3)
-        k = qkv[:, :, :, 1].permute(0, 2, 1, 3)
-        v = qkv[:, :, :, 2].permute(0, 2, 1, 3)
-        # write into the cache
-        cache_k[:, :, start_pos:start_pos + S] = k
-        cache_v[:, :, start_pos:start_pos + S] = v
-        total = start_pos + S
-        kc = cache_k[:, :, :total]
-        vc = cache_v[:, :, :total]
-        if S == total:
-            o = ops.flash_attention(q.contiguous(), kc, vc, causal=True)
-        else:
-            # decode: queries attend to the whole cache (no mask needed for
-            # a single new position; for S>1 chunks fall back to causal
-            # offset via full recompute of the chunk)
-            o = ops.flash_attention(q.contiguous(), kc, vc,
-                                    causal=(S > 1))
-        o = o.permute(0, 2, 1, 3).reshape(B, S, h * d)
-        return self.out(o)
-
-    def forward(self, x, cache_k, cache_v, start_pos: int):
-        x = x + self._attn(self.ln1(x), cache_k, cache_v, start_pos)
-        h = self.fc1(self.ln2(x))
-        h = torch.nn.functional.relu(h)
-        x = x + self.fc2(h)
-        return x
-
-    @torch.no_grad()
-    def _attn_decode_varlen(self, x, cache_k, cache_v, lens, cap=None):
-        """One token per slot at PER-SLOT positions (continuous
-        batching): scatter k/v at lens[b], attend with kv_lens=lens+1.
-        `cap` fixes the attended cache capacity WITHOUT the host-synced
-        lens.max() — required under hipGraph capture (the varlen kernel
-        masks past each slot's device-side length anyway)."""
-        B, S, _ = x.shape
-        assert S == 1
-        h, d = self.heads_per_rank, self.head_dim
-        qkv = self.qkv(x).view(B, 1, h, 3, d)
-        q = qkv[:, :, :, 0].permute(0, 2, 1, 3)
-        k = qkv[:, :, :, 1].permute(0, 2, 1, 3)
-        v = qkv[:, :, :, 2].permute(0, 2, 1, 3)
-        bidx = torch.arange(B, device=x.device)
-        cache_k[bidx, :, lens] = k[:, :, 0]
-        cache_v[bidx, :, lens] = v[:, :, 0]
-        total = cap if cap is not None else int(lens.max()) + 1
-        o = ops.flash_attention_varlen(q.contiguous(),
-                                       cache_k[:, :, :total],
-                                       cache_v[:, :, :total], lens + 1)
-        o = o.permute(0, 2, 1, 3).reshape(B, 1, h * d)
-        return self.out(o)
-
-    @torch.no_grad()
-    def forward_decode_varlen(self, x, cache_k, cache_v, lens, cap=None):
-        x = x + self._attn_decode_varlen(self.ln1(x), cache_k, cache_v,
-                                         lens, cap)
-        h = self.fc1(self.ln2(x))
-        h = torch.nn.functional.relu(h)
-        return x + self.fc2(h)
+        super().__init__(cfg, mesh, axis, dtype, device, idx, init_seed,
+                         gelu=False, parallel=False)
 
 
-class OPTModel(nn.Module, GenerationMixin):
-    """TP-sharded OPT decoder with generation support (greedy/beam from
-    GenerationMixin)."""
+class OPTModel(CachedDecoder):
+    """TP-sharded OPT decoder: learned positions with a +2 offset."""
+
+    block_cls = OPTBlock
 
     def __init__(self, cfg: OPTConfig, mesh: Optional[DeviceMesh] = None,
                  axis: int = 1, dtype=torch.float32, device=None,
                  init_seed: int = 0):
-        super().__init__()
-        self.cfg = cfg
-        assert cfg.head_dim <= 256, (
-            f"head_dim {cfg.head_dim} > 256 unsupported; dims in "
-            "(128, 256] use the blocked hipBLASLt attention path")
-        self.mesh, self.axis = mesh, axis
-        tp = mesh.axis_size(axis) if mesh is not None else 1
-        self.heads_per_rank = cfg.num_heads // tp
-        self.wte = VocabParallelEmbedding(cfg.vocab_size, cfg.hidden_size,
-                                          mesh, axis, dtype=dtype,
-                                          device=device, init_seed=init_seed,
-                                          init_tag="wte")
-        # OPT uses learned positions with a +2 offset
-        from ..parallel.layers import tag_seed
+        super().__init__(cfg, mesh, axis, dtype, device, init_seed)
         g = torch.Generator()
         g.manual_seed(tag_seed(init_seed, "wpe"))
         wpe = torch.empty(cfg.max_seq_len + 2, cfg.hidden_size,
                           dtype=torch.float32).normal_(0, 0.02, generator=g)
         self.wpe = nn.Parameter(wpe.to(dtype=dtype, device=device))
-        self.blocks = nn.ModuleList([
-            OPTBlock(cfg, mesh, axis, dtype, device, i, init_seed)
-            for i in range(cfg.num_layers)
-        ])
-        self.ln_f = LayerNorm(cfg.hidden_size, cfg.layernorm_eps, dtype,
-                              device)
-        self.lm_head = ColumnParallelLinear(cfg.hidden_size, cfg.vocab_size,
-                                            mesh, axis, bias=False,
-                                            dtype=dtype, device=device,
-                                            init_seed=init_seed,
-                                            init_tag="lm_head")
-        self.lm_head._fp8_exclude = True  # logits GEMM stays bf16
-        self.dtype = dtype
-        self.device_ = device
 
-    def new_cache(self, batch: int, max_len: Optional[int] = None
-                  ) -> KVCache:
-        return KVCache(self.cfg, self.cfg.num_layers, batch,
-                       self.heads_per_rank, self.dtype, self.device_,
-                       max_len=max_len)
+    def _embed(self, ids, pos):
+        if isinstance(pos, int):
+            return self.wte(ids) + self.wpe[2 + pos:2 + pos + ids.shape[1]]
+        return self.wte(ids) + self.wpe[2 + pos].unsqueeze(1)
 
     def forward_train(self, ids: torch.Tensor) -> torch.Tensor:
         """Differentiable causal forward WITHOUT the KV cache (training/
         finetuning path — cache writes are no-grad buffers and would
         silently detach the k/v projections).  Returns full-sequence
         logits [B, S, vocab/tp]."""
-        from .. import ops
-        B, S = ids.shape
-        x = self.wte(ids) + self.wpe[2:2 + S]
-        h, d = self.heads_per_rank, self.cfg.head_dim
-        for blk in self.blocks:
-            y = blk.ln1(x)
-            qkv = blk.qkv(y).view(B, S, h, 3, d)
-            q = qkv[:, :, :, 0].permute(0, 2, 1, 3).contiguous()
-            k = qkv[:, :, :, 1].permute(0, 2, 1, 3).contiguous()
-            v = qkv[:, :, :, 2].permute(0, 2, 1, 3).contiguous()
-            o = ops.flash_attention(q, k, v, causal=True)
-            o = o.permute(0, 2, 1, 3).reshape(B, S, h * d)
-            x = x + blk.out(o)
-            hmid = torch.nn.functional.relu(blk.fc1(blk.ln2(x)))
-            x = x + blk.fc2(hmid)
+        x = self._run_blocks(self._embed(ids, 0), None, 0)
         return self.lm_head(self.ln_f(x))
-
-    @torch.no_grad()
-    def forward_prefill(self, ids: torch.Tensor, lens: torch.Tensor,
-                        cache: KVCache) -> torch.Tensor:
-        """Batched variable-length prefill: ids [n, Smax] right-padded
-        prompts, lens [n] true lengths.  ONE causal pass prefills every
-        slot (padding rows only contaminate padding rows under the
-        causal mask); returns each slot's last-real-position logits
-        [n, vocab/tp].  The continuous batcher admits all pending
-        requests through this instead of per-slot prefills
-        (reference 1-D batching, opt_model_1d.py)."""
-        B, S = ids.shape
-        x = self.wte(ids) + self.wpe[2:2 + S]
-        for i, blk in enumerate(self.blocks):
-            x = blk(x, cache.k[i], cache.v[i], 0)
-        cache.length = S
-        idx = (lens.to(ids.device) - 1).clamp(min=0)
-        x_last = x[torch.arange(B, device=ids.device), idx].unsqueeze(1)
-        return self.lm_head(self.ln_f(x_last))[:, 0]
-
-    def forward_step(self, ids: torch.Tensor, cache: KVCache
-                     ) -> torch.Tensor:
-        """ids [B, S] (prefill) or [B, 1] (decode). Returns last-position
-        logits [B, vocab/tp]."""
-        B, S = ids.shape
-        pos = cache.length
-        # chunked decode with history would need a causal-offset mask in the
-        # kernel; prefill (pos==0) and single-token decode cover serving
-        assert pos == 0 or S == 1, "chunked decode with history unsupported"
-        x = self.wte(ids) + self.wpe[2 + pos:2 + pos + S]
-        for i, blk in enumerate(self.blocks):
-            x = blk(x, cache.k[i], cache.v[i], pos)
-        cache.length += S
-        x = self.ln_f(x[:, -1:])
-        return self.lm_head(x)[:, 0]
-
-    @torch.no_grad()
-    def forward_decode(self, tok: torch.Tensor, cache: KVCache,
-                       lens: torch.Tensor, cap=None) -> torch.Tensor:
-        """Varlen decode (continuous batching): tok [B, 1] next token per
-        slot, lens [B] tokens already cached per slot.  Returns logits
-        [B, vocab/tp].  The caller owns per-slot length bookkeeping
-        (cache.length is unused on this path)."""
-        x = self.wte(tok) + self.wpe[2 + lens].unsqueeze(1)
-        for i, blk in enumerate(self.blocks):
-            x = blk.forward_decode_varlen(x, cache.k[i], cache.v[i], lens,
-                                          cap)
-        return self.lm_head(self.ln_f(x))[:, 0]
-
-    @torch.no_grad()
-    def graphed_decoder(self, prompt_ids: torch.Tensor,
-                        max_new_tokens: int) -> "_GraphedDecode":
-        """Prefill + capture now; `.run()` replays the decode loop
-        (single use — the cache advances).  Lets benchmarks time the
-        replay loop separately from the one-time capture."""
-        return _GraphedDecode(self, prompt_ids, max_new_tokens)
-
-    @torch.no_grad()
-    def generate_graphed(self, prompt_ids: torch.Tensor,
-                         max_new_tokens: int) -> torch.Tensor:
-        """Greedy generate with the DECODE STEP hipGraph-captured.
-
-        Eager decode is host-bound (~23 us/op measured: OPT-66B 28.1
-        ms/token = ~1200 op dispatches) — capturing one whole decode
-        step (including the greedy-token feedback and the device-side
-        length increment) reduces the per-token host work to one graph
-        replay + one token copy-out.  Everything dynamic lives in
-        device tensors updated in place: the varlen attention masks by
-        lens, the cache scatter and wpe gather index by lens, and the
-        cache view is a fixed capacity (prompt + max_new_tokens).
-        Single-mesh (tp=1) path; requires CUDA."""
-        return self.graphed_decoder(prompt_ids, max_new_tokens).run()
-
-
-class _GraphedDecode:
-    """See OPTModel.generate_graphed."""
-
-    @torch.no_grad()
-    def __init__(self, model, prompt_ids, max_new_tokens):
-        assert prompt_ids.is_cuda and (
-            model.mesh is None or model.mesh.axis_size(model.axis) == 1)
-        B, S0 = prompt_ids.shape
-        self.model, self.prompt_ids = model, prompt_ids
-        self.max_new = max_new_tokens
-        cap = S0 + max_new_tokens
-        cache = model.new_cache(B, max_len=cap)
-        logits = model.forward_step(prompt_ids, cache)
-        tok = self.tok = model.greedy_token(logits).reshape(B, 1).clone()
-        lens = self.lens = torch.full((B,), S0, dtype=torch.long,
-                                      device=prompt_ids.device)
-        out = self.out = torch.empty(B, max_new_tokens,
-                                     dtype=prompt_ids.dtype,
-                                     device=prompt_ids.device)
-        out[:, 0] = tok[:, 0]
-
-        def step():
-            lg = model.forward_decode(tok, cache, lens, cap=cap)
-            nxt = model.greedy_token(lg).reshape(B, 1)
-            lens.add_(1)
-            tok.copy_(nxt)
-
-        # warmup on a side stream (standard capture recipe), then capture
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            step()
-        torch.cuda.current_stream().wait_stream(side)
-        # roll back the warmup step's state mutations
-        lens.fill_(S0)
-        tok[:, 0] = out[:, 0]
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            step()
-
-    @torch.no_grad()
-    def run(self) -> torch.Tensor:
-        # capture ran no work; replay i generates token i+1
-        for i in range(1, self.max_new):
-            self.graph.replay()
-            self.out[:, i] = self.tok[:, 0]
-        return torch.cat([self.prompt_ids, self.out], dim=1)
-

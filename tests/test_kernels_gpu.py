@@ -489,6 +489,50 @@ def test_bloom_generation_on_gpu():
                                rtol=5e-2, atol=5e-2)
 
 
+def test_bloom_per_slot_decode_on_gpu():
+    """BLOOM through forward_decode (continuous batching): two slots at
+    unequal lengths decode in one varlen call with slopes; each slot's
+    logits match that slot decoded alone through forward_step.  Same
+    tolerance as test_bloom_generation_on_gpu."""
+    import alpa_amd as aa
+    from alpa_amd.models.bloom import BloomConfig, BloomModel
+    from alpa_amd.serve.batching import _SlotCacheView
+    aa.init()
+    cfg = BloomConfig(hidden_size=128, num_layers=2, num_heads=2,
+                      vocab_size=128, max_seq_len=32)
+    m = BloomModel(cfg, None, 1, torch.bfloat16, "cuda", init_seed=7)
+    torch.manual_seed(20)
+    lens = torch.tensor([5, 8], device="cuda")
+    cache = m.new_cache(2)
+    views, cur = [], []
+    with torch.no_grad():
+        for b, n in enumerate(lens.tolist()):
+            views.append(_SlotCacheView(cache, b))
+            ids = torch.randint(0, 128, (1, n), device="cuda")
+            cur.append(m.greedy_token(m.forward_step(ids, views[b])))
+        cur = torch.stack(cur)                       # [2, 1]
+        logits = m.forward_decode(cur, cache, lens)
+        for b in range(2):
+            solo = m.forward_step(cur[b:b + 1], views[b])
+            torch.testing.assert_close(logits[b:b + 1].float(),
+                                       solo.float(), rtol=5e-2, atol=5e-2)
+
+
+@pytest.mark.parametrize("D", [64, 128, 256])
+def test_attention_one_visible_key(D):
+    """One query, one key: the softmax weight is exactly 1, so o is v bit
+    for bit on every route flash_attention takes — causal (prefill kernel;
+    the blocked path at D=256) and non-causal (split-KV decode kernel).
+    This is what lets the cached decoders use causal = S > 1 for a
+    one-token prompt."""
+    from alpa_amd import ops
+    torch.manual_seed(21)
+    q, k, v = (torch.randn(2, 2, 1, D, device="cuda", dtype=torch.bfloat16)
+               for _ in range(3))
+    assert torch.equal(ops.flash_attention(q, k, v, causal=True), v)
+    assert torch.equal(ops.flash_attention(q, k, v, causal=False), v)
+
+
 def test_attention_varlen_gpu(ext):
     """Per-batch kv_lens masking in the fwd kernel vs per-request
     separate kernel calls."""

@@ -373,17 +373,13 @@ def test_varlen_attention_reference():
         torch.testing.assert_close(o[b:b + 1], ob, rtol=1e-5, atol=1e-5)
 
 
-def test_continuous_batching_matches_per_request():
-    """Staggered requests through the slot batcher produce exactly the
-    tokens each request would get alone (greedy)."""
+def _check_batcher_matches_solo(m, max_batch):
     from alpa_amd.serve.batching import ContinuousBatcher, GenRequest
-    torch.manual_seed(21)
-    m = build_opt()
-    prompts = [torch.randint(0, CFG.vocab_size, (n,))
+    prompts = [torch.randint(0, m.cfg.vocab_size, (n,))
                for n in (5, 9, 3, 7)]
     want = [m.generate(p.view(1, -1), max_new_tokens=6)[0, len(p):]
             for p in prompts]
-    cb = ContinuousBatcher(m, max_batch=2)
+    cb = ContinuousBatcher(m, max_batch=max_batch)
     reqs = [GenRequest(p, max_new_tokens=6) for p in prompts]
     for r in reqs:
         cb.submit(r)
@@ -391,6 +387,39 @@ def test_continuous_batching_matches_per_request():
     for r, w in zip(reqs, want):
         assert r.done
         assert r.output == w.tolist(), (r.output, w.tolist())
+
+
+def test_continuous_batching_matches_per_request():
+    """Staggered requests through the slot batcher produce exactly the
+    tokens each request would get alone (greedy)."""
+    torch.manual_seed(21)
+    _check_batcher_matches_solo(build_opt(), max_batch=2)
+
+
+@pytest.mark.parametrize("max_batch", [2, 3])
+@pytest.mark.parametrize("seed", [21, 31])
+def test_continuous_batching_matches_per_request_bloom(seed, max_batch):
+    """The same through BLOOM: per-slot decode with ALiBi slopes (the
+    bias of slot b is taken from its own length, not the batch's)."""
+    from alpa_amd.models.bloom import BloomConfig, BloomModel
+    torch.manual_seed(seed)
+    cfg = BloomConfig(hidden_size=64, num_layers=2, num_heads=4,
+                      vocab_size=96, max_seq_len=64)
+    _check_batcher_matches_solo(BloomModel(cfg, init_seed=19), max_batch)
+
+
+def test_codegen_forward_decode_not_implemented():
+    """Rotary takes one int position for the whole batch: per-slot decode
+    must refuse, by name, not rotate every slot to a wrong position."""
+    from alpa_amd.models.codegen import CodeGenConfig, CodeGenModel
+    cfg = CodeGenConfig(hidden_size=64, num_layers=2, num_heads=4,
+                        vocab_size=96, max_seq_len=64, rotary_dim=8)
+    m = CodeGenModel(cfg, init_seed=17)
+    cache = m.new_cache(2, max_len=16)
+    assert cache.k[0].shape[2] == 16
+    with pytest.raises(NotImplementedError, match="per-slot positions"):
+        m.forward_decode(torch.zeros(2, 1, dtype=torch.long), cache,
+                         torch.tensor([3, 5]))
 
 
 def test_continuous_batching_eos_frees_slot():
@@ -542,3 +571,120 @@ def test_continuous_batching_batched_admission_matches_per_request():
     for r, w in zip(reqs, want):
         assert r.done
         assert r.output == w.tolist(), (r.output, w.tolist())
+
+
+# ---------------------------------------------------------------------------
+# Parameter names are an interface: serve/weights.py and checkpoints address
+# them by name.  The lists were recorded from the three separate model files
+# before they were folded onto models/decoder.py.
+# ---------------------------------------------------------------------------
+
+_STATE_DICT_PINS = {
+    "opt": [
+        ("blocks.0.fc1.bias", (256,)),
+        ("blocks.0.fc1.weight", (256, 64)),
+        ("blocks.0.fc2.bias", (64,)),
+        ("blocks.0.fc2.weight", (64, 256)),
+        ("blocks.0.ln1.bias", (64,)),
+        ("blocks.0.ln1.weight", (64,)),
+        ("blocks.0.ln2.bias", (64,)),
+        ("blocks.0.ln2.weight", (64,)),
+        ("blocks.0.out.bias", (64,)),
+        ("blocks.0.out.weight", (64, 64)),
+        ("blocks.0.qkv.bias", (192,)),
+        ("blocks.0.qkv.weight", (192, 64)),
+        ("blocks.1.fc1.bias", (256,)),
+        ("blocks.1.fc1.weight", (256, 64)),
+        ("blocks.1.fc2.bias", (64,)),
+        ("blocks.1.fc2.weight", (64, 256)),
+        ("blocks.1.ln1.bias", (64,)),
+        ("blocks.1.ln1.weight", (64,)),
+        ("blocks.1.ln2.bias", (64,)),
+        ("blocks.1.ln2.weight", (64,)),
+        ("blocks.1.out.bias", (64,)),
+        ("blocks.1.out.weight", (64, 64)),
+        ("blocks.1.qkv.bias", (192,)),
+        ("blocks.1.qkv.weight", (192, 64)),
+        ("lm_head.weight", (96, 64)),
+        ("ln_f.bias", (64,)),
+        ("ln_f.weight", (64,)),
+        ("wpe", (66, 64)),
+        ("wte.weight", (96, 64)),
+    ],
+    "bloom": [
+        ("blocks.0.fc1.bias", (256,)),
+        ("blocks.0.fc1.weight", (256, 64)),
+        ("blocks.0.fc2.bias", (64,)),
+        ("blocks.0.fc2.weight", (64, 256)),
+        ("blocks.0.ln1.bias", (64,)),
+        ("blocks.0.ln1.weight", (64,)),
+        ("blocks.0.ln2.bias", (64,)),
+        ("blocks.0.ln2.weight", (64,)),
+        ("blocks.0.out.bias", (64,)),
+        ("blocks.0.out.weight", (64, 64)),
+        ("blocks.0.qkv.bias", (192,)),
+        ("blocks.0.qkv.weight", (192, 64)),
+        ("blocks.1.fc1.bias", (256,)),
+        ("blocks.1.fc1.weight", (256, 64)),
+        ("blocks.1.fc2.bias", (64,)),
+        ("blocks.1.fc2.weight", (64, 256)),
+        ("blocks.1.ln1.bias", (64,)),
+        ("blocks.1.ln1.weight", (64,)),
+        ("blocks.1.ln2.bias", (64,)),
+        ("blocks.1.ln2.weight", (64,)),
+        ("blocks.1.out.bias", (64,)),
+        ("blocks.1.out.weight", (64, 64)),
+        ("blocks.1.qkv.bias", (192,)),
+        ("blocks.1.qkv.weight", (192, 64)),
+        ("lm_head.weight", (96, 64)),
+        ("ln_emb.bias", (64,)),
+        ("ln_emb.weight", (64,)),
+        ("ln_f.bias", (64,)),
+        ("ln_f.weight", (64,)),
+        ("wte.weight", (96, 64)),
+    ],
+    "codegen": [
+        ("blocks.0.fc1.bias", (256,)),
+        ("blocks.0.fc1.weight", (256, 64)),
+        ("blocks.0.fc2.bias", (64,)),
+        ("blocks.0.fc2.weight", (64, 256)),
+        ("blocks.0.ln.bias", (64,)),
+        ("blocks.0.ln.weight", (64,)),
+        ("blocks.0.out.bias", (64,)),
+        ("blocks.0.out.weight", (64, 64)),
+        ("blocks.0.qkv.bias", (192,)),
+        ("blocks.0.qkv.weight", (192, 64)),
+        ("blocks.1.fc1.bias", (256,)),
+        ("blocks.1.fc1.weight", (256, 64)),
+        ("blocks.1.fc2.bias", (64,)),
+        ("blocks.1.fc2.weight", (64, 256)),
+        ("blocks.1.ln.bias", (64,)),
+        ("blocks.1.ln.weight", (64,)),
+        ("blocks.1.out.bias", (64,)),
+        ("blocks.1.out.weight", (64, 64)),
+        ("blocks.1.qkv.bias", (192,)),
+        ("blocks.1.qkv.weight", (192, 64)),
+        ("lm_head.weight", (96, 64)),
+        ("ln_f.bias", (64,)),
+        ("ln_f.weight", (64,)),
+        ("wte.weight", (96, 64)),
+    ],
+}
+
+
+@pytest.mark.parametrize("family", sorted(_STATE_DICT_PINS))
+def test_state_dict_names_and_shapes_pinned(family):
+    from alpa_amd.models.bloom import BloomConfig, BloomModel
+    from alpa_amd.models.codegen import CodeGenConfig, CodeGenModel
+    tiny = dict(hidden_size=64, num_layers=2, num_heads=4, vocab_size=96,
+                max_seq_len=64)
+    m = {"opt": build_opt,
+         "bloom": lambda: BloomModel(BloomConfig(**tiny), init_seed=19),
+         "codegen": lambda: CodeGenModel(
+             CodeGenConfig(rotary_dim=8, **tiny), init_seed=17)}[family]()
+    got = sorted((k, tuple(v.shape)) for k, v in m.state_dict().items())
+    assert got == _STATE_DICT_PINS[family]
+    # the non-persistent buffers stay out of the state_dict and stay put
+    buffers = {"opt": [], "bloom": ["slopes"],
+               "codegen": ["rot_sin", "rot_cos"]}[family]
+    assert [n for n, _ in m.named_buffers()] == buffers
