@@ -40,13 +40,29 @@ class GlobalConfig:
         default_factory=lambda: os.environ.get("ALPA_AMD_FP8_WGRAD",
                                                "1") == "1")
     #: hand-written decode GEMV (ops/csrc/skinny_gemm.hip) for
-    #: inference GEMMs with <= 8 tokens.  "auto" (default) enables it
+    #: inference GEMMs with <= 8 tokens (9..64: below).  "auto" (default) enables it
     #: only inside the MEASURED end-to-end win envelope — hidden-5120-
     #: class shapes (K <= 5120 or the matching 4x ffn K), where OPT-13B
     #: decode drops 11.85 -> 8.58 ms/token bf16 / 7.70 fp8.  hipBLASLt
     #: already streams >= 5 TB/s at hidden >= 7168 (30B/66B measured
     #: parity-to-loss end-to-end), so those stay on the library.
-    #: ALPA_AMD_SKINNY=1 forces it everywhere, =0 disables.
+    #: For 9..64 tokens the MFMA skinny GEMM (ops/csrc/skinny_mfma.hip)
+    #: serves the same packed weights inside its envelope (N % 64 == 0,
+    #: K % 256 == 0).  "auto" adds it on top of the rules above only
+    #: where tools/skinny_bench.py measured a win over the library's bf16
+    #: GEMM beyond the 6 % run-to-run spread (best legal split, two
+    #: passes, M = 16/32/64; docs/BENCHMARK.md, "MFMA skinny GEMM"):
+    #:   - K >= 2N (5120x20480): all tiers, 1.66-1.90x bf16, 2.12-2.95x
+    #:     e4m3;
+    #:   - e4m3 weights (fp8_gemm), any other shape: up to 32 tokens
+    #:     (1.15-2.69x); 33..64 stay on the library (0.81-1.09x);
+    #:   - bf16, N <= K (5120x5120): up to 32 tokens (1.16-1.34x);
+    #:     33..64 stay on the library (0.94-0.98x);
+    #:   - bf16, N > K (qkv 15360x5120, fc1 20480x5120) stays on the
+    #:     library: 0.66-0.98x, except 1.78x at exactly M = 16 on fc1.
+    #: End to end (serve_bench) was not measured for these batch sizes.
+    #: ALPA_AMD_SKINNY=1 forces both kernels everywhere inside their
+    #: envelopes, =0 disables both.
     skinny_gemm: str = field(
         default_factory=lambda: os.environ.get("ALPA_AMD_SKINNY",
                                                "auto"))

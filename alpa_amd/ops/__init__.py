@@ -926,6 +926,53 @@ def _skinny_splits(N: int, K: int, M: int) -> Optional[int]:
     return lds_ok[-1]
 
 
+#: LDS bytes the MFMA kernel's staged x slice may take (SKINNY_MFMA_LDS_MAX
+#: in csrc/launchers.h: the CU's 160 KB)
+_SKINNY_MFMA_LDS = 160 * 1024
+
+
+def _skinny_mfma_mt(M: int) -> int:
+    """The MFMA kernel's token tier: 16, 32 or 64."""
+    return 16 if M <= 16 else 32 if M <= 32 else 64
+
+
+def _skinny_mfma_legal_splits(K: int, MT: int) -> List[int]:
+    """Ascending split-K factors the MFMA kernel takes: K % 256 == 0, s
+    divides K/256 (a k-slice is whole 8-k-step pipeline rounds) and the
+    LDS x slice MT * (K/s + 16) * 2 bytes fits _SKINNY_MFMA_LDS."""
+    if K <= 0 or K % 256:
+        return []
+    q = K // 256
+    return [s for s in range(1, q + 1)
+            if q % s == 0 and MT * (K // s + 16) * 2 <= _SKINNY_MFMA_LDS]
+
+
+@functools.lru_cache(maxsize=None)
+def _skinny_mfma_splits(N: int, K: int, M: int) -> Optional[int]:
+    """Split-K factor for the MFMA skinny GEMM (grid ceil(N/256) x s
+    workgroups of 4 waves): a legal split (_skinny_mfma_legal_splits).
+    None = outside the kernel's envelope."""
+    if not 9 <= M <= 64 or N <= 0 or N % 64:
+        return None
+    legal = _skinny_mfma_legal_splits(K, _skinny_mfma_mt(M))
+    if not legal:
+        return None
+    wgs = -(-N // 256)
+    # same two-rule shape as _skinny_splits, thresholds from the
+    # tools/skinny_bench.py sweep (docs/BENCHMARK.md): the best split of
+    # every swept shape has 100-400 workgroups and k-slices of 512-2048 --
+    # every further split adds M*N*4 bytes of partials to write and read
+    # back.  So: the SMALLEST split with >= 192 workgroups (3/4 of the 256
+    # CUs) and k-slices <= 2048, else the smallest that fills alone
+    for s in legal:
+        if wgs * s >= 192 and K // s <= 2048:
+            return s
+    for s in legal:
+        if wgs * s >= 192:
+            return s
+    return legal[-1]
+
+
 def _skinny_cache(module, weight: torch.Tensor, fp8: bool):
     """Packed [K/8, N, 8] weight (+ e4m3 scale), cached on the module and
     keyed on the parameter version (in-place optimizer updates bump it)."""
@@ -950,13 +997,35 @@ def _skinny_cache(module, weight: torch.Tensor, fp8: bool):
     return wp, scale
 
 
+def _skinny_mfma_auto(N: int, K: int, M: int, fp8: bool) -> bool:
+    """Where "auto" routes 9..64 tokens to the MFMA kernel: the shape
+    classes and token tiers in which tools/skinny_bench.py measured it
+    faster than the library's bf16 GEMM by more than the 6 % run-to-run
+    spread (table in docs/BENCHMARK.md, rule on global_config.skinny_gemm).
+      - K >= 2N (ffn down-projections, 5120 x 20480): every tier, bf16
+        1.66-1.90x, e4m3 2.12-2.95x.
+      - e4m3 weights otherwise: tiers 16 and 32 (1.15-2.69x on all five
+        other shapes); tier 64 stays on the library (0.81-1.09x).
+      - bf16 otherwise: tiers 16 and 32 at N <= K (5120 x 5120: 1.16-
+        1.34x).  N > K (qkv, fc1) stays on the library: 0.81-0.98x, but
+        for 20480 x 5120 at M = 16 (1.78x against a library outlier that
+        M < 16 was not measured for).  Tier 64 stays too (0.66-0.98x)."""
+    if K >= 2 * N:
+        return True
+    if M > 32:
+        return False
+    return fp8 or N <= K
+
+
 def skinny_ok(x: torch.Tensor, weight: torch.Tensor, module=None) -> bool:
-    """Gate for the decode GEMV kernel (csrc/skinny_gemm.hip): inference
-    only, M <= 8 tokens, 64-aligned dims.  Measured (tools/
-    skinny_bench.py sweep): the kernel wins 1.5-3.1x at M<=4-8 (up to
+    """Gate for the packed decode kernels, inference only.  Up to 8 tokens:
+    the dot2 GEMV (csrc/skinny_gemm.hip), 64-aligned dims.  Measured
+    (tools/skinny_bench.py sweep): it wins 1.5-3.1x at M<=4-8 (up to
     6.2 TB/s bf16 / 4.6 TB/s-of-fp8-bytes) but the per-m VALU work makes
-    M >= 16 issue-bound (SIMD-32 units: 2 cyc/VALU instr for wave64) —
-    hipBLASLt keeps those; an MFMA 16x16x32 variant is the next step."""
+    M >= 16 issue-bound (SIMD-32 units: 2 cyc/VALU instr for wave64).
+    9..64 tokens: the MFMA 16x16x32 kernel (csrc/skinny_mfma.hip) inside
+    its envelope (N % 64 == 0, K % 256 == 0, a legal split); in "auto"
+    only where _skinny_mfma_auto says it was measured to win."""
     from ..global_env import global_config
     mode = global_config.skinny_gemm
     if mode in ("0", False) or torch.is_grad_enabled():
@@ -980,42 +1049,66 @@ def skinny_ok(x: torch.Tensor, weight: torch.Tensor, module=None) -> bool:
         if not fp8:
             return False
     m = x.numel() // x.shape[-1]
-    return (m <= 8 and N % 64 == 0 and K % 64 == 0
-            and _skinny_splits(N, K, m) is not None)
+    if m <= 8:
+        return (N % 64 == 0 and K % 64 == 0
+                and _skinny_splits(N, K, m) is not None)
+    # 9..64 tokens: the MFMA kernel, inside its envelope (and, in auto,
+    # inside the measured win envelope: see global_config.skinny_gemm)
+    if _skinny_mfma_splits(N, K, m) is None or x.data_ptr() % 16:
+        return False
+    if mode != "auto":
+        return True
+    fp8 = bool(global_config.fp8_gemm and
+               not getattr(module, "_fp8_exclude", False))
+    return _skinny_mfma_auto(N, K, m, fp8)
 
 
 _SKINNY_TUNED = {}
 
 
-def _skinny_tune(wp, x2, scale, N, K, MT):
-    """One-time per-(shape, MT, dtype) split autotune: the best split
-    factor is shape- AND M-dependent (measured: rounds=16 wins 66B fp8
-    decode, the fill-first choice wins 13B batch-1), so time the legal
+def _skinny_tune(wp, x2, scale, N, K, MT, kernel="dot2"):
+    """One-time per-(shape, MT, dtype, kernel) split autotune: the best
+    split factor is shape- AND M-dependent (measured: rounds=16 wins 66B
+    fp8 decode, the fill-first choice wins 13B batch-1), so time the legal
     candidates once and cache — the ~2 ms cost amortizes over the
-    decode loop, like a library heuristic cache."""
-    key = (N, K, MT, scale is not None)
+    decode loop, like a library heuristic cache.  `kernel` is "dot2"
+    (skinny_gemm, MT its padded tier) or "mfma" (skinny_gemm_mfma, MT its
+    token tier); the tag keeps their equal tiers apart in the cache."""
+    key = (N, K, MT, scale is not None, kernel)
     got = _SKINNY_TUNED.get(key)
     if got is not None:
         return got
-    legal = _skinny_legal_splits(K, MT)
-    cands = sorted({
-        s for s in (
+    if kernel == "mfma":
+        gemm = hip_ops().skinny_gemm_mfma
+        legal = _skinny_mfma_legal_splits(K, MT)
+        wgs = -(-N // 256)
+        picks = (
+            next((c for c in legal
+                  if wgs * c >= 192 and K // c <= 2048), None),
+            next((c for c in legal if wgs * c >= 96), None),
+            next((c for c in legal if wgs * c >= 384), None),
+            legal[-1])
+    else:
+        gemm = hip_ops().skinny_gemm
+        legal = _skinny_legal_splits(K, MT)
+        picks = (
             next((c for c in reversed(legal)
                   if K // 8 // c >= 16 and (N // 64) * c >= 1024), None),
             next((c for c in legal if (N // 64) * c >= 2560), None),
             next((c for c in legal if K // 8 // c <= 32), None),
-            legal[-1]) if s is not None})
+            legal[-1])
+    cands = sorted({s for s in picks if s is not None})
     if len(cands) == 1:
         _SKINNY_TUNED[key] = cands[0]
         return cands[0]
     best, best_t = cands[0], float("inf")
     for c in cands:
-        hip_ops().skinny_gemm(wp, x2, scale, None, N, K, c)  # warm
+        gemm(wp, x2, scale, None, N, K, c)  # warm
         t0 = torch.cuda.Event(True)
         t1 = torch.cuda.Event(True)
         t0.record()
         for _ in range(10):
-            hip_ops().skinny_gemm(wp, x2, scale, None, N, K, c)
+            gemm(wp, x2, scale, None, N, K, c)
         t1.record()
         t1.synchronize()
         dt = t0.elapsed_time(t1)
@@ -1027,7 +1120,8 @@ def _skinny_tune(wp, x2, scale, N, K, MT):
 
 def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
                   bias: Optional[torch.Tensor], module) -> torch.Tensor:
-    """y = x @ W^T (+bias) through the packed decode GEMV.  fp8 weights
+    """y = x @ W^T (+bias) through the packed decode kernels: the dot2
+    GEMV up to 8 tokens, the MFMA skinny GEMM for 9..64.  fp8 weights
     (half the bytes/token) when global_config.fp8_gemm is on and the
     module isn't _fp8_exclude; split-K fp32 partials are stored and
     reduced in a fixed order by a finalize launch (deterministic, no
@@ -1040,11 +1134,19 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
     shape = x.shape
     x2 = x.reshape(-1, K).contiguous()
     b = bias.contiguous() if bias is not None else None
-    MT = _skinny_mt(x2.shape[0])
-    if torch.cuda.is_current_stream_capturing():
-        splits = _SKINNY_TUNED.get((N, K, MT, scale is not None)) \
-            or _skinny_splits(N, K, x2.shape[0])
+    M = x2.shape[0]
+    # up to 8 tokens: the dot2 kernel; 9..64 (skinny_ok has checked the
+    # envelope): the MFMA kernel, over the same packed weights
+    if M <= 8:
+        kernel, gemm = "dot2", hip_ops().skinny_gemm
+        MT, rule = _skinny_mt(M), _skinny_splits
     else:
-        splits = _skinny_tune(wp, x2, scale, N, K, MT)
-    y = hip_ops().skinny_gemm(wp, x2, scale, b, N, K, splits)
+        kernel, gemm = "mfma", hip_ops().skinny_gemm_mfma
+        MT, rule = _skinny_mfma_mt(M), _skinny_mfma_splits
+    if torch.cuda.is_current_stream_capturing():
+        splits = _SKINNY_TUNED.get((N, K, MT, scale is not None, kernel)) \
+            or rule(N, K, M)
+    else:
+        splits = _skinny_tune(wp, x2, scale, N, K, MT, kernel)
+    y = gemm(wp, x2, scale, b, N, K, splits)
     return y.reshape(*shape[:-1], N)

@@ -362,6 +362,59 @@ at::Tensor skinny_gemm(const at::Tensor& wp, const at::Tensor& x,
   return y;
 }
 
+// The same product for 9 <= M <= 64 through the MFMA kernel
+// (skinny_mfma.hip), over the same packed wp.  x goes in unpadded.  One
+// launch when splits == 1 (bias and the bf16 cast fused), else fp32
+// partials [splits, M, N] and the deterministic finalize.
+at::Tensor skinny_gemm_mfma(const at::Tensor& wp, const at::Tensor& x,
+                            const c10::optional<at::Tensor>& wscale,
+                            const c10::optional<at::Tensor>& bias,
+                            int64_t N, int64_t K, int64_t splits) {
+  TORCH_CHECK(N > 0 && N % 64 == 0, "N must be a positive multiple of 64");
+  TORCH_CHECK(K > 0 && K % 256 == 0, "K must be a positive multiple of 256");
+  const bool fp8 = wscale.has_value();
+  if (fp8) {
+    check_device(wp, "wp", wp);
+    TORCH_CHECK(wp.element_size() == 1,
+                "wp must hold one-byte elements when wscale is given");
+    TORCH_CHECK(wp.is_contiguous() && wp.numel() == N * K,
+                "wp must be contiguous with N*K elements");
+    check_vec(*wscale, "wscale", at::kFloat, 1, wp);
+  } else {
+    check_vec(wp, "wp", at::kBFloat16, N * K, wp);
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(wp.const_data_ptr()) % 16 == 0,
+              "wp must be 16-byte aligned");
+  if (bias.has_value()) {
+    check_vec(*bias, "bias", at::kBFloat16, N, wp);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(bias->const_data_ptr()) % 8 == 0,
+                "bias must be 8-byte aligned");
+  }
+  auto [M, Kx] = check_rows(x, "x", 256, wp);
+  TORCH_CHECK(x.dim() == 2 && Kx == K, "x must be [M, K]");
+  TORCH_CHECK(M >= 9 && M <= 64, "x must have 9 to 64 rows, got ", M);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.const_data_ptr()) % 16 == 0,
+              "x must be 16-byte aligned");
+  const int64_t MT = M <= 16 ? 16 : M <= 32 ? 32 : 64;
+  // what the kernel's 8-k-step pipeline and its LDS x slice take
+  TORCH_CHECK(splits >= 1 && (K / 256) % splits == 0 &&
+                  MT * (K / splits + 16) * 2 <= SKINNY_MFMA_LDS_MAX,
+              "splits must divide K/256 and leave MT*(K/splits+16)*2 <= ",
+              SKINNY_MFMA_LDS_MAX, " bytes of LDS, got ", splits);
+  at::Tensor part;
+  if (splits > 1)
+    part = at::empty({splits, M, N}, x.options().dtype(at::kFloat));
+  auto y = at::empty({M, N}, x.options());
+  HIP_OK(launch_skinny_mfma(
+      wp.const_data_ptr(), x.const_data_ptr(),
+      splits > 1 ? (float*)part.mutable_data_ptr() : nullptr,
+      bias.has_value() ? bias->const_data_ptr() : nullptr,
+      y.mutable_data_ptr(),
+      fp8 ? (const float*)wscale->const_data_ptr() : nullptr, M, N, K,
+      (int)splits, cur_stream()));
+  return y;
+}
+
 // -------------------------------- AdamW ----------------------------------
 
 void adamw_step_raw(const at::Tensor& descs, const at::Tensor& chunks,
@@ -1062,6 +1115,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("t"), py::arg("out_dtype") = py::none());
   m.def("skinny_gemm", &skinny_gemm,
         "decode GEMV over packed weights (gfx950)");
+  m.def("skinny_gemm_mfma", &skinny_gemm_mfma,
+        "MFMA decode GEMM for 9..64 tokens over packed weights (gfx950)");
   m.def("adamw_step_raw", &adamw_step_raw, "multi-tensor AdamW (gfx950)",
         py::arg("descs"), py::arg("chunks"), py::arg("step"), py::arg("lr"),
         py::arg("beta1"), py::arg("beta2"), py::arg("eps"),

@@ -90,6 +90,18 @@ hipError_t launch_skinny_gemm(const void* wp, const void* x, float* part,
                               int64_t MT, int64_t N, int64_t K, int splits,
                               int fp8, hipStream_t stream);
 
+// ---- skinny_mfma.hip ----
+// 9 <= M <= 64, N % 64 == 0, K % 256 == 0, splits divides K/256 and the
+// staged x slice MT * (K/splits + 16) * 2 bytes (MT = 16/32/64, the tier of
+// M) is at most SKINNY_MFMA_LDS_MAX.  part_or_null: fp32 [splits, M, N] iff
+// splits > 1.  x is [M, K], unpadded.
+#define SKINNY_MFMA_LDS_MAX (160 * 1024)
+hipError_t launch_skinny_mfma(const void* wp, const void* x,
+                              float* part_or_null, const void* bias_or_null,
+                              void* y, const float* wscale_or_null,
+                              int64_t M, int64_t N, int64_t K, int splits,
+                              hipStream_t stream);
+
 // ---- cross_entropy.hip ----
 hipError_t launch_ce_fwd(const void* logits, const int64_t* targets,
                          float* loss, float* lse, int64_t N, int64_t V,

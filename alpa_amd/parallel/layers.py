@@ -190,7 +190,8 @@ class ColumnParallelLinear(nn.Module):
         x = copy_to_tp(x, self.mesh, self.axis)
         if ops.skinny_ok(x, self.weight, self):
             assert not defer_gelu
-            # decode-shaped inference (M <= 64): packed GEMV kernel
+            # decode-shaped inference: the packed kernels (dot2 GEMV up to
+            # 8 tokens, MFMA skinny GEMM for 9..64)
             if self.gelu:
                 return ops.bias_gelu(
                     ops.skinny_linear(x, self.weight, None, self),

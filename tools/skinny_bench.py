@@ -1,13 +1,34 @@
-"""Numerics + bandwidth of the skinny decode GEMV (csrc/skinny_gemm.hip)
-vs torch.matmul at OPT-13B decode shapes."""
+"""Numerics + bandwidth of the skinny decode kernels vs torch.matmul at
+decode shapes: the dot2 GEMV (csrc/skinny_gemm.hip) and, for 9..64 tokens
+inside its envelope, the MFMA skinny GEMM (csrc/skinny_mfma.hip) as a third
+column.  Every column is the time of one whole call (all its launches).
+SKINNY_SWEEP=1 sweeps the legal splits of both kernels, SKINNY_REPEAT=n
+prints the whole table n times (the spread between the copies is the
+run-to-run noise); HBM bandwidth is the bound of these GEMMs, so the floor
+is weight bytes / SKINNY_PEAK_TBS (default 8 TB/s, the MI355X HBM peak)."""
+import os
 import sys
 import time
 
 import torch
 
 sys.path.insert(0, ".")
-from alpa_amd.ops import _skinny_splits
+from alpa_amd.ops import (_skinny_mfma_legal_splits, _skinny_mfma_mt,
+                          _skinny_mfma_splits, _skinny_splits)
 from alpa_amd.ops._backend import hip_ops
+
+PEAK_TBS = float(os.environ.get("SKINNY_PEAK_TBS", "8.0"))
+
+
+def bench(fn, iters=300):
+    for _ in range(30):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e6
 
 
 def run(M, N, K, fp8):
@@ -24,22 +45,11 @@ def run(M, N, K, fp8):
         scale = None
         wp = w.view(N, K // 8, 8).permute(1, 0, 2).contiguous()
         wref = w
-    import os
     s = _skinny_splits(N, K, M)
     sweep = os.environ.get("SKINNY_SWEEP") == "1"
     y = hip_ops().skinny_gemm(wp, x, scale, None, N, K, s)
     ref = x.float() @ wref.float().t()
     rel = (y - ref).abs().mean() / ref.abs().mean().clamp_min(1e-9)
-
-    def bench(fn, iters=300):
-        for _ in range(30):
-            fn()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / iters * 1e6
 
     t_k = bench(lambda: hip_ops().skinny_gemm(wp, x, scale, None, N, K, s))
     if sweep:
@@ -55,21 +65,40 @@ def run(M, N, K, fp8):
                 t_k, s = t2, s2
     t_t = bench(lambda: x @ w.t())
     bytes_w = N * K * (1 if fp8 else 2)
-    print(f"M={M:3d} N={N:6d} K={K:6d} {'fp8' if fp8 else 'bf16'} "
-          f"splits={s:2d}: rel={rel.item():.4f}  kernel {t_k:7.1f} us "
-          f"({bytes_w / t_k / 1e6:5.2f} TB/s)  torch {t_t:7.1f} us  "
-          f"speedup {t_t / t_k:4.2f}x")
+    line = (f"M={M:3d} N={N:6d} K={K:6d} {'fp8' if fp8 else 'bf16'} "
+            f"splits={s:2d}: rel={rel.item():.4f}  kernel {t_k:7.1f} us "
+            f"({bytes_w / t_k / 1e6:5.2f} TB/s)  torch {t_t:7.1f} us  "
+            f"speedup {t_t / t_k:4.2f}x")
+    sm = _skinny_mfma_splits(N, K, M)
+    if sm is not None:
+        def mfma(c):
+            return hip_ops().skinny_gemm_mfma(wp, x, scale, None, N, K, c)
+        rel_m = (mfma(sm) - ref).abs().mean() / ref.abs().mean() \
+            .clamp_min(1e-9)
+        rule, t_m = sm, bench(lambda: mfma(sm))
+        t_rule = t_m
+        if sweep:
+            for s2 in _skinny_mfma_legal_splits(K, _skinny_mfma_mt(M)):
+                t2 = bench(lambda: mfma(s2), 100)
+                if t2 < t_m:
+                    t_m, sm = t2, s2
+        floor = bytes_w / PEAK_TBS / 1e6
+        line += (f"  |  mfma splits={sm:2d} (rule {rule:2d}: {t_rule:6.1f} us)"
+                 f" rel={rel_m.item():.4f} {t_m:7.1f} us "
+                 f"({bytes_w / t_m / 1e6:5.2f} TB/s, {floor / t_m:4.0%} of "
+                 f"the HBM floor)  vs torch {t_t / t_m:4.2f}x  "
+                 f"vs dot2 {t_k / t_m:4.2f}x")
+    print(line, flush=True)
 
 
-import os as _os
-
-_shapes = _os.environ.get("SKINNY_SHAPES")
+_shapes = os.environ.get("SKINNY_SHAPES")
 SHAPES = ([tuple(map(int, t.split("x"))) for t in _shapes.split(",")]
           if _shapes else [(5120, 5120), (15360, 5120), (20480, 5120),
                            (5120, 20480)])
 MS = tuple(int(m) for m in
-           _os.environ.get("SKINNY_MS", "4,16,64").split(","))
-for fp8 in (False, True):
-    for (N, K) in SHAPES:
-        for M in MS:
-            run(M, N, K, fp8)
+           os.environ.get("SKINNY_MS", "4,16,64").split(","))
+for rep in range(int(os.environ.get("SKINNY_REPEAT", "1"))):
+    for fp8 in (False, True):
+        for (N, K) in SHAPES:
+            for M in MS:
+                run(M, N, K, fp8)
