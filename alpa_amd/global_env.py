@@ -90,6 +90,26 @@ class GlobalConfig:
         default_factory=lambda: os.environ.get("ALPA_AMD_DECODE_ATTN",
                                                "auto"))
 
+    #: e4m3 KV cache for the cached decoders (models/decoder.py): KVCache
+    #: holds bytes plus one fp32 scale per cached row (per slot, head and
+    #: position; no calibration), rows are written by the fused
+    #: quantize-and-append kernel (ops/csrc/kv_cache_fp8.hip) and read by
+    #: the e4m3 split-KV decode kernel (ops/csrc/attention_decode_fp8.hip).
+    #: Prefill attends over the fresh bf16 k/v as before.  Half the cache
+    #: memory and half the bytes a decode step streams, at the cost of
+    #: e4m3 rounding of k and v (docs/KERNELS.md, "e4m3 KV cache").
+    #: tools/decode_attn_bench.py on one MI355X (table in
+    #: docs/BENCHMARK.md, "e4m3 KV cache"): against the bf16 decode kernel
+    #: the e4m3 one is 1.83-1.91x at batch 32, length 2048 (OPT-13B heads:
+    #: 243.9 -> 130.7 us; spread 0.01-0.16) and 1.45-1.92x at batch 8,
+    #: length 2048; parity to 1.3x at batch 1; 0.93-0.98x where 2048 keys
+    #: of capacity hold 128-key slots at head_dim 128 (dispatch-bound).  The
+    #: fused append takes 3.3-4.0 us against 11.5-14.9 us for the two
+    #: index_put scatters.  End to end (serve_bench) was not measured.
+    #: Off by default; ALPA_AMD_KV_FP8=1 turns it on.
+    kv_cache_fp8: bool = field(
+        default_factory=lambda: _env_bool("ALPA_AMD_KV_FP8", False))
+
     #: compute dX with the bf16 MASTER weight instead of the fp8 wqt
     #: cache: halves the fp8 weight-cache footprint (the +30 GB dual
     #: cache at 15B pushes hipGraph capture OOM -> eager, see

@@ -28,27 +28,72 @@ from .gpt import LayerNorm
 class KVCache:
     """Per-layer preallocated cache [B, heads/tp, max_len, d] (analog of
     the reference's cache-as-DistributedArrays kept on mesh,
-    wrapper.py:356-371)."""
+    wrapper.py:356-371).
+
+    fp8 (global_config.kv_cache_fp8): k and v hold float8_e4m3fn bytes and
+    k_scale, v_scale [B, heads/tp, max_len] one fp32 scale per cached row
+    (ops.kv_cache_append_fp8 writes them, ops.flash_attention_decode_fp8
+    reads them); otherwise k_scale and v_scale are None."""
 
     def __init__(self, cfg, num_layers: int, batch: int,
                  heads_per_rank: int, dtype, device,
-                 max_len: Optional[int] = None):
+                 max_len: Optional[int] = None, fp8: bool = False):
         d = cfg.head_dim
         max_len = max_len or cfg.max_seq_len
-        self.k = [torch.zeros(batch, heads_per_rank, max_len, d,
-                              dtype=dtype, device=device)
-                  for _ in range(num_layers)]
-        self.v = [torch.zeros(batch, heads_per_rank, max_len, d,
-                              dtype=dtype, device=device)
-                  for _ in range(num_layers)]
+        self.fp8 = fp8
+
+        def rows():
+            if not fp8:
+                return torch.zeros(batch, heads_per_rank, max_len, d,
+                                   dtype=dtype, device=device)
+            return torch.zeros(batch, heads_per_rank, max_len, d,
+                               dtype=torch.uint8,
+                               device=device).view(torch.float8_e4m3fn)
+
+        self.k = [rows() for _ in range(num_layers)]
+        self.v = [rows() for _ in range(num_layers)]
+        self.k_scale = self.v_scale = None
+        if fp8:
+            self.k_scale, self.v_scale = (
+                [torch.zeros(batch, heads_per_rank, max_len,
+                             dtype=torch.float32, device=device)
+                 for _ in range(num_layers)] for _ in range(2))
         self.length = 0
+
+    def _lists(self):
+        return [t for t in (self.k, self.v, self.k_scale, self.v_scale)
+                if t is not None]
 
     def reorder(self, beam_idx: torch.Tensor):
         """Beam-search cache reorder (reference index-select executables,
-        mesh_executable.py:1168)."""
-        for i in range(len(self.k)):
-            self.k[i] = self.k[i].index_select(0, beam_idx)
-            self.v[i] = self.v[i].index_select(0, beam_idx)
+        mesh_executable.py:1168); the scales of an fp8 cache move with
+        their rows."""
+        for ts in self._lists():
+            for i in range(len(ts)):
+                t = ts[i]
+                if t.dtype == torch.float8_e4m3fn:   # gather the bytes
+                    ts[i] = t.view(torch.uint8).index_select(
+                        0, beam_idx).view(t.dtype)
+                else:
+                    ts[i] = t.index_select(0, beam_idx)
+
+    def slots(self, s0: int, n: int) -> "KVCache":
+        """A cache over slots s0 .. s0+n-1 that shares this one's memory
+        (length 0), so a prefill writes straight into the shared buffers."""
+        view = object.__new__(KVCache)
+        view.fp8, view.length = self.fp8, 0
+        view.k_scale = view.v_scale = None
+        for name in ("k", "v") + (("k_scale", "v_scale") if self.fp8 else ()):
+            setattr(view, name, [t[s0:s0 + n] for t in getattr(self, name)])
+        return view
+
+    def layer(self, i: int):
+        """(cache_k, cache_v) of layer i as DecoderBlock takes them: the
+        tensors, or (bytes, scales) pairs for an fp8 cache."""
+        if self.fp8:
+            return ((self.k[i], self.k_scale[i]),
+                    (self.v[i], self.v_scale[i]))
+        return self.k[i], self.v[i]
 
 
 class DecoderBlock(nn.Module):
@@ -99,7 +144,9 @@ class DecoderBlock(nn.Module):
         if rotate is not None:
             q, k = rotate(q, pos), rotate(k, pos)
         q = q.contiguous()
-        if cache_k is None:
+        if isinstance(cache_k, tuple):
+            o = self._attn_fp8(q, k, v, cache_k, cache_v, pos, slopes, cap)
+        elif cache_k is None:
             o = ops.flash_attention(q, k.contiguous(), v.contiguous(),
                                     causal=True, alibi_slopes=slopes)
         elif isinstance(pos, int):
@@ -121,6 +168,28 @@ class DecoderBlock(nn.Module):
                                            cache_v[:, :, :total], pos + 1,
                                            alibi_slopes=slopes)
         return self.out(o.permute(0, 2, 1, 3).reshape(B, S, h * d))
+
+    def _attn_fp8(self, q, k, v, cache_k, cache_v, pos, slopes, cap):
+        """The cached branches of _attn over an e4m3 cache: cache_k and
+        cache_v are (bytes, scales).  Prefill attends over the fresh bf16
+        k/v, which is all there is to see at pos == 0, and then appends;
+        a single-token step appends first and reads the cache through the
+        e4m3 decode kernel with kv_lens = pos + 1."""
+        (k8, ks), (v8, vs) = cache_k, cache_v
+        B, S = q.shape[0], q.shape[2]
+        if S > 1:
+            assert isinstance(pos, int) and pos == 0
+            ops.kv_cache_append_fp8(k, v, k8, ks, v8, vs, 0)
+            return ops.flash_attention(q, k.contiguous(), v.contiguous(),
+                                       causal=True, alibi_slopes=slopes)
+        ops.kv_cache_append_fp8(k, v, k8, ks, v8, vs, pos)
+        if isinstance(pos, int):
+            total, lens = pos + 1, None
+        else:
+            total, lens = cap or int(pos.max()) + 1, pos + 1
+        return ops.flash_attention_decode_fp8(
+            q, k8[:, :, :total], ks[:, :, :total], v8[:, :, :total],
+            vs[:, :, :total], kv_lens=lens, alibi_slopes=slopes)
 
     def _mlp(self, y):
         y = self.fc1(y)
@@ -189,16 +258,16 @@ class CachedDecoder(nn.Module, GenerationMixin):
     def _run_blocks(self, x, cache, pos, cap=None):
         kw = self._attn_args()
         for i, blk in enumerate(self.blocks):
-            ck, cv = (cache.k[i], cache.v[i]) if cache is not None \
-                else (None, None)
+            ck, cv = cache.layer(i) if cache is not None else (None, None)
             x = blk(x, ck, cv, pos, cap=cap, **kw)
         return x
 
     def new_cache(self, batch: int, max_len: Optional[int] = None
                   ) -> KVCache:
+        from ..global_env import global_config
         return KVCache(self.cfg, self.cfg.num_layers, batch,
                        self.heads_per_rank, self.dtype, self.device_,
-                       max_len=max_len)
+                       max_len=max_len, fp8=global_config.kv_cache_fp8)
 
     def forward_step(self, ids: torch.Tensor, cache: KVCache
                      ) -> torch.Tensor:

@@ -14,7 +14,9 @@ slots), moe_dispatch and moe_combine.  add_layer_norm_fp8 and bias_gelu_fp8
 are the LayerNorm and GeLU forwards with the fp8 quantize of ops/fp8.py
 folded in.  flash_attention_decode is the split-KV attention kernel for
 single-token queries, which flash_attention and flash_attention_varlen use
-for every decode step.
+for every decode step.  kv_cache_append_fp8 and flash_attention_decode_fp8
+are the write and the read side of the e4m3 KV cache (one fp32 scale per
+cached row), which global_config.kv_cache_fp8 turns on in the decoders.
 
 Kernel-level contract mirrors the reference's compiled-HLO op inventory
 (GEMM+epilogue, attention, LayerNorm, fused Adam,
@@ -35,7 +37,9 @@ __all__ = [
     "layer_norm", "add_layer_norm", "bias_gelu", "add_layer_norm_fp8",
     "bias_gelu_fp8", "flash_attention",
     "flash_attention_qkv", "flash_attention_decode", "decode_attn_ok",
-    "DECODE_ATTN_CHUNK", "softmax_cross_entropy",
+    "DECODE_ATTN_CHUNK", "kv_cache_append_fp8",
+    "flash_attention_decode_fp8", "decode_attn_fp8_ok",
+    "softmax_cross_entropy",
     "softmax_cross_entropy_partial", "softmax_cross_entropy_combine",
     "softmax_cross_entropy_shard_bwd", "vocab_ce_fused_ok", "fused_adamw",
     "multi_tensor_sumsq",
@@ -409,6 +413,137 @@ def flash_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
             q, k, v, scale, alibi_slopes,
             None if lens is None else lens.contiguous())[0]
     o, _ = ref.attention_fwd(q, k, v, False, scale, alibi_slopes, lens)
+    return o
+
+
+def _kv8_ok(c8: torch.Tensor, cs: torch.Tensor, first: torch.Tensor,
+            align: int) -> bool:
+    """One half of an e4m3 cache: bytes [B, h, L, d] float8_e4m3fn with a
+    contiguous head dim and rows aligned to `align` bytes, and its scales
+    [B, h, L] fp32, both on the device of `first`."""
+    if not (c8.is_cuda and c8.device == first.device
+            and c8.dtype == torch.float8_e4m3fn and c8.dim() == 4
+            and c8.stride(3) == 1):
+        return False
+    if c8.data_ptr() % align != 0 or not all(
+            c8.shape[i] <= 1 or c8.stride(i) % align == 0 for i in range(3)):
+        return False
+    return (cs.is_cuda and cs.device == first.device
+            and cs.dtype == torch.float32 and cs.shape == c8.shape[:3])
+
+
+def decode_attn_fp8_ok(q: torch.Tensor, k8: torch.Tensor,
+                       k_scale: torch.Tensor, v8: torch.Tensor,
+                       v_scale: torch.Tensor) -> bool:
+    """Envelope of the e4m3-cache decode kernel
+    (csrc/attention_decode_fp8.hip; the binding checks the same).  It is
+    decode_attn_ok with the cache in bytes: q bf16 [B, h, 1, d] on the GPU,
+    k8, v8 [B, h, Skv, d] float8_e4m3fn views with a contiguous head dim, d
+    a multiple of 16 up to 256, every q row and every cache row 16-byte
+    aligned; plus k_scale, v_scale fp32 [B, h, Skv] on the same device (any
+    strides)."""
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 4
+            and q.stride(3) == 1 and _rows_aligned16(q)):
+        return False
+    D = q.shape[3]
+    if q.shape[2] != 1 or D % 16 != 0 or not 16 <= D <= 256 \
+            or q.shape[0] * q.shape[1] > 65535:
+        return False
+    if not (_kv8_ok(k8, k_scale, q, 16) and _kv8_ok(v8, v_scale, q, 16)):
+        return False
+    if k8.shape != v8.shape or k8.shape[:2] != q.shape[:2] \
+            or k8.shape[3] != D:
+        return False
+    return use_hip(q)
+
+
+def _kv_append_ok(k, v, k8, k_scale, v8, v_scale, pos) -> bool:
+    """Envelope of csrc/kv_cache_fp8.hip: k, v bf16 [B, h, S, d] views on
+    the GPU with a contiguous head dim and 16-byte-aligned rows, d a multiple
+    of 16 in [16, 256], cache rows 8-byte aligned, pos an int or a contiguous
+    int32/int64 [B] on the device."""
+    for t in (k, v):
+        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
+                and t.stride(3) == 1 and _rows_aligned16(t)):
+            return False
+    D = k.shape[3]
+    if k.shape != v.shape or D % 16 != 0 or not 16 <= D <= 256:
+        return False
+    if not (_kv8_ok(k8, k_scale, k, 8) and _kv8_ok(v8, v_scale, k, 8)):
+        return False
+    if k8.shape != v8.shape or k8.shape[:2] != k.shape[:2] \
+            or k8.shape[3] != D:
+        return False
+    if torch.is_tensor(pos) and not (
+            pos.device == k.device and pos.is_contiguous()
+            and pos.dtype in (torch.int32, torch.int64)
+            and pos.shape == (k.shape[0],)):
+        return False
+    return use_hip(k)
+
+
+@torch.no_grad()
+def kv_cache_append_fp8(k: torch.Tensor, v: torch.Tensor, k8: torch.Tensor,
+                        k_scale: torch.Tensor, v8: torch.Tensor,
+                        v_scale: torch.Tensor, pos) -> None:
+    """Quantize the new rows k, v [B, h, S, d] to e4m3 and write them into
+    the cache k8, v8 [B, h, max_len, d] (float8_e4m3fn) with k_scale, v_scale
+    [B, h, max_len] (fp32), in place: row (b, h, s) goes to position
+    pos_b + s, where pos is one int or an int tensor [B].
+
+    Every row carries its own scale: scale = amax(|x|) / 448 and bytes =
+    e4m3_rne(x / scale), both in fp32, saturating.  An all-zero row stores
+    scale = 1.  A row that holds a NaN or an Inf stores scale = NaN and the
+    byte 0x7F throughout, so it dequantizes to NaN and poisons the slot that
+    attends to it instead of being clamped.  A row whose position is
+    negative or >= max_len is skipped.  Older rows are never touched.
+
+    On the GPU this is one launch of the gfx950 kernel for K and V together;
+    it reads strided views (the k and v of a packed qkv projection) in place
+    and takes pos from the device without a host read, so it can be captured
+    in a graph.  On CPU or outside the kernel's envelope it is
+    reference.kv_cache_append_fp8."""
+    if _kv_append_ok(k, v, k8, k_scale, v8, v_scale, pos):
+        if torch.is_tensor(pos):
+            hip_ops().kv_cache_append(k, v, k8, k_scale, v8, v_scale, 0, pos)
+        else:
+            hip_ops().kv_cache_append(k, v, k8, k_scale, v8, v_scale,
+                                      int(pos), None)
+        return
+    ref.kv_cache_append_fp8(k, v, k8, k_scale, v8, v_scale, pos)
+
+
+@torch.no_grad()
+def flash_attention_decode_fp8(q: torch.Tensor, k8: torch.Tensor,
+                               k_scale: torch.Tensor, v8: torch.Tensor,
+                               v_scale: torch.Tensor,
+                               kv_lens: Optional[torch.Tensor] = None,
+                               scale: Optional[float] = None,
+                               alibi_slopes: Optional[torch.Tensor] = None
+                               ) -> torch.Tensor:
+    """flash_attention_decode over the e4m3 cache that kv_cache_append_fp8
+    writes: q [B, h, 1, d] attends to the first kv_lens[b] (default all Skv)
+    rows of k8, v8 [B, h, Skv, d] with per-row scales [B, h, Skv]; returns
+    o [B, h, 1, d] in q's dtype.  Inference only.
+
+    Inside decode_attn_fp8_ok this is the split-KV gfx950 kernel with the
+    chunking of the bf16 one (DECODE_ATTN_CHUNK); it streams half the bytes.
+    All math is fp32: s = (q . k8_row) * k_scale[row] * scale, P is not
+    rounded, v_scale[row] is folded into p.  Rows at or past a slot's length
+    are never loaded, scales included, and a slot's output bits depend only
+    on that slot's own q, visible rows and scales, length, d, scale and
+    slope.  A slot of length 0 gives o = 0; a visible row with a NaN scale
+    gives a NaN output.  On CPU or outside the envelope it is
+    reference.attention_decode_fp8."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    lens = None if kv_lens is None else kv_lens.to(dtype=torch.int32)
+    if decode_attn_fp8_ok(q, k8, k_scale, v8, v_scale):
+        return hip_ops().attn_decode_fp8(
+            q, k8, k_scale, v8, v_scale, scale, alibi_slopes,
+            None if lens is None else lens.contiguous())[0]
+    o, _ = ref.attention_decode_fp8(q, k8, k_scale, v8, v_scale, scale,
+                                    alibi_slopes, lens)
     return o
 
 

@@ -50,20 +50,8 @@
 // SIMD (the intent: several workgroups per CU, so that a CU has loads of
 // more than one chunk in flight), 1552 / 2576 / 4624 B of LDS, no scratch.
 // Combine kernel: 10 VGPRs, 8 waves per SIMD, no LDS, no scratch.
-#include "attn_strides.h"
-#include "common.h"
+#include "attn_decode_common.h"
 #include "launchers.h"
-
-#define DEC_THREADS 256
-#define DEC_WAVES (DEC_THREADS / 64)
-
-// Keys per chunk for the instantiation padded to Dp.  A compile-time
-// constant per Dp: it must never depend on B, H, Skv or the device, or the
-// invariance above is gone.  ops.DECODE_ATTN_CHUNK mirrors it.
-template <int Dp>
-struct DecodeChunk {
-  static constexpr int value = 128;
-};
 
 __device__ __forceinline__ void unpack_bf16x8(bf16x8 x, float* f) {
   union {
@@ -76,27 +64,6 @@ __device__ __forceinline__ void unpack_bf16x8(bf16x8 x, float* f) {
     f[2 * i] = __uint_as_float(c.u[i] << 16);
     f[2 * i + 1] = __uint_as_float(c.u[i] & 0xffff0000u);
   }
-}
-
-// The one place a row is normalised, shared by the combine kernel and the
-// single-chunk shortcut.  Contraction is off so that both callers round in
-// the same places whatever surrounds the call.
-__device__ __forceinline__ void attn_decode_finish(float a, float L, float M,
-                                                   short* o_elem,
-                                                   float* lse_elem) {
-#pragma clang fp contract(off)
-  const float inv_l = (L > 0.f) ? 1.0f / L : 0.f;
-  if (o_elem != nullptr) *o_elem = f2bf(a * inv_l);
-  if (lse_elem != nullptr) {
-    const float lg = __logf(L);
-    *lse_elem = (L > 0.f) ? M + lg : -INFINITY;
-  }
-}
-
-__device__ __forceinline__ int decode_len(const int* kv_lens, int batch,
-                                          int Skv) {
-  const int len = kv_lens != nullptr ? kv_lens[batch] : Skv;
-  return min(max(len, 0), Skv);
 }
 
 // Dp: head dim padded to 64/128/256; CH: keys per chunk; AL: ALiBi bias.
@@ -258,34 +225,6 @@ __global__ __launch_bounds__(DEC_THREADS) void attn_decode_partial_kernel(
   }
   if (t < D)
     ws[(int64_t)gridDim.y * n_chunks * 2 + slot * D + t] = a;
-}
-
-// One workgroup per (batch, head); thread t owns head-dim column t.
-template <int CH>
-__global__ __launch_bounds__(DEC_THREADS) void attn_decode_combine_kernel(
-    const float* __restrict__ ws, short* __restrict__ o,
-    float* __restrict__ lse_out, int H, int Skv, int D, int n_chunks,
-    const int* __restrict__ kv_lens, AttnStrides st) {
-  const int bh = blockIdx.x;
-  const int batch = bh / H, head = bh % H;
-  const int t = threadIdx.x;
-  const int len = decode_len(kv_lens, batch, Skv);
-  const int live = (len + CH - 1) / CH;  // chunks that wrote their slot
-  const float* ml = ws + (int64_t)bh * n_chunks * 2;
-  const float* accs = ws + (int64_t)gridDim.x * n_chunks * 2 +
-                      (int64_t)bh * n_chunks * D;
-  float M = -INFINITY;
-  for (int c = 0; c < live; ++c) M = fmaxf(M, ml[2 * c]);
-  float L = 0.f, a = 0.f;
-  for (int c = 0; c < live; ++c) {
-    const float mc = ml[2 * c];
-    const float w = (mc == -INFINITY) ? 0.f : __expf(mc - M);
-    L = fmaf(w, ml[2 * c + 1], L);
-    if (t < D) a = fmaf(w, accs[(int64_t)c * D + t], a);
-  }
-  short* op = o + batch * st.ob + head * st.oh;
-  attn_decode_finish(a, L, M, t < D ? op + t : nullptr,
-                     t == 0 ? lse_out + bh : nullptr);
 }
 
 extern "C" {

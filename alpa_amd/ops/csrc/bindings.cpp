@@ -667,6 +667,105 @@ std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k,
   return {o, lse};
 }
 
+// ------------------------------ e4m3 KV cache ------------------------------
+// The cache of kv_cache_fp8.hip: bytes [B,H,L,D] e4m3 with a contiguous head
+// dim and rows aligned to `align` bytes, and one fp32 scale per row, [B,H,L].
+void check_kv8(const at::Tensor& c8, const at::Tensor& cs, const char* name,
+               const char* scale_name, int64_t B, int64_t H, int64_t L,
+               int64_t D, int64_t align, const at::Tensor& first) {
+  check_typed(c8, name, at::kFloat8_e4m3fn, first);
+  TORCH_CHECK(c8.dim() == 4 && c8.stride(3) == 1, name,
+              " must be 4-D [B,H,L,D] with a contiguous head-dim");
+  const int64_t want[4] = {B, H, L, D};
+  for (int i = 0; i < 4; ++i)
+    TORCH_CHECK(want[i] < 0 || c8.size(i) == want[i], name,
+                " must have size ", want[i], " in dimension ", i, ", got ",
+                c8.size(i));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(c8.const_data_ptr()) % align == 0,
+              name, " must be ", align, "-byte aligned");
+  for (int i = 0; i < 3; ++i)
+    TORCH_CHECK(c8.size(i) <= 1 || c8.stride(i) % align == 0, name,
+                ": the stride of dimension ", i, " must be a multiple of ",
+                align, " bytes, got ", c8.stride(i));
+  check_typed(cs, scale_name, at::kFloat, first);
+  TORCH_CHECK(cs.dim() == 3 && cs.size(0) == c8.size(0) &&
+                  cs.size(1) == c8.size(1) && cs.size(2) == c8.size(2),
+              scale_name, " must be [B,H,L], one scale per row of ", name);
+}
+
+// Quantize k, v [B,H,S,D] bf16 views per row to e4m3 and write row (b,h,s)
+// at position pos_b + s of the cache (kv_cache_fp8.hip); in place.  pos_dev:
+// int32 or int64 [B] on the device, else pos_b = pos_host.  Positions
+// outside [0, max_len) are skipped.
+void kv_cache_append(const at::Tensor& k, const at::Tensor& v, at::Tensor k8,
+                     at::Tensor k_scale, at::Tensor v8, at::Tensor v_scale,
+                     int64_t pos_host,
+                     const c10::optional<at::Tensor>& pos_dev =
+                         c10::nullopt) {
+  check_bhsd(k, "k", -1, -1, -1, -1, k);
+  const int64_t B = k.size(0), H = k.size(1), S = k.size(2), D = k.size(3);
+  check_bhsd(v, "v", B, H, S, D, k);
+  TORCH_CHECK(D >= 16 && D % 16 == 0 && D <= 256,
+              "head_dim must be a multiple of 16 in [16, 256], got ", D);
+  check_rows_aligned16(k, "k");
+  check_rows_aligned16(v, "v");
+  check_kv8(k8, k_scale, "k8", "k_scale", B, H, -1, D, 8, k);
+  const int64_t L = k8.size(2);
+  check_kv8(v8, v_scale, "v8", "v_scale", B, H, L, D, 8, k);
+  int pos_kind = 0;
+  if (given(pos_dev)) {
+    const bool i32 = pos_dev->scalar_type() == at::kInt;
+    TORCH_CHECK(i32 || pos_dev->scalar_type() == at::kLong,
+                "pos must be int32 or int64");
+    check_vec(*pos_dev, "pos", pos_dev->scalar_type(), B, k);
+    pos_kind = i32 ? 1 : 2;
+  }
+  const auto strides = bhs_strides(k, v, k8, v8, k_scale, v_scale);
+  HIP_OK(launch_kv_cache_append(
+      k.const_data_ptr(), v.const_data_ptr(), k8.mutable_data_ptr(),
+      (float*)k_scale.mutable_data_ptr(), v8.mutable_data_ptr(),
+      (float*)v_scale.mutable_data_ptr(), B, H, S, D, L, pos_host,
+      opt_ptr(pos_dev), pos_kind, strides.data(), cur_stream()));
+}
+
+// attn_decode over the e4m3 cache (attention_decode_fp8.hip): q [B,H,1,D]
+// bf16, k8 and v8 [B,H,Skv,D] e4m3 views with 16-byte-aligned rows, k_scale
+// and v_scale [B,H,Skv] fp32 views.  Returns (o [B,H,1,D] bf16, lse [B,H,1]).
+std::vector<at::Tensor> attn_decode_fp8(
+    const at::Tensor& q, const at::Tensor& k8, const at::Tensor& k_scale,
+    const at::Tensor& v8, const at::Tensor& v_scale, double scale,
+    const c10::optional<at::Tensor>& alibi = c10::nullopt,
+    const c10::optional<at::Tensor>& kv_lens = c10::nullopt) {
+  check_bhsd(q, "q", -1, -1, -1, -1, q);
+  const int64_t B = q.size(0), H = q.size(1), D = q.size(3);
+  TORCH_CHECK(q.size(2) == 1, "q must hold one query row per head, got ",
+              q.size(2));
+  TORCH_CHECK(D > 0 && D % 16 == 0 && D <= 256,
+              "head_dim must be a multiple of 16 up to 256, got ", D);
+  TORCH_CHECK(B * H <= 65535, "q: at most 65535 (batch, head) pairs, got ",
+              B * H);
+  check_rows_aligned16(q, "q");
+  check_kv8(k8, k_scale, "k8", "k_scale", B, H, -1, D, 16, q);
+  const int64_t Skv = k8.size(2);
+  check_kv8(v8, v_scale, "v8", "v_scale", B, H, Skv, D, 16, q);
+  if (given(alibi)) check_vec(*alibi, "alibi", at::kFloat, H, q);
+  if (given(kv_lens)) check_vec(*kv_lens, "kv_lens", at::kInt, B, q);
+  auto f32 = q.options().dtype(at::kFloat);
+  auto o = at::empty({B, H, 1, D}, q.options());
+  auto lse = at::empty({B, H, 1}, f32);
+  if (B * H == 0) return {o, lse};
+  auto ws = at::empty({attn_decode_workspace_floats(B, H, Skv, D)}, f32);
+  const auto strides = bhs_strides(q, k8, v8, o, k_scale, v_scale);
+  HIP_OK(launch_attn_decode_fp8(
+      q.const_data_ptr(), k8.const_data_ptr(),
+      (const float*)k_scale.const_data_ptr(), v8.const_data_ptr(),
+      (const float*)v_scale.const_data_ptr(), o.mutable_data_ptr(),
+      (float*)lse.mutable_data_ptr(), (float*)ws.mutable_data_ptr(), B, H,
+      Skv, D, (float)scale, (const float*)opt_ptr(alibi),
+      (const int*)opt_ptr(kv_lens), strides.data(), cur_stream()));
+  return {o, lse};
+}
+
 // Blocked attention forward for head_dim > 128 (the fused kernel tiles
 // head_dim in registers up to 128): q-block loop, scores via bf16
 // hipBLASLt GEMMs, fp32 softmax, never materializes more than one
@@ -1096,7 +1195,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // 8: attn_decode and attn_decode_chunk added
   // 9: layer_norm_bwd, add_layer_norm_bwd, bias_gelu_bwd and colsum_bf16
   // take an optional out_dtype (fp32 or bf16) for the vectors they reduce
-  m.attr("ABI_VERSION") = 9;
+  // 10: kv_cache_append and attn_decode_fp8 added (e4m3 KV cache)
+  m.attr("ABI_VERSION") = 10;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)",
         py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),
@@ -1151,6 +1251,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_chunk",
         [](int64_t D) { return attn_decode_chunk(D); },
         "keys per split-KV chunk of attn_decode at head_dim D");
+  m.def("kv_cache_append", &kv_cache_append,
+        "quantize k, v rows to e4m3 and append them to the cache (gfx950)",
+        py::arg("k"), py::arg("v"), py::arg("k8"), py::arg("k_scale"),
+        py::arg("v8"), py::arg("v_scale"), py::arg("pos"),
+        py::arg("pos_dev") = py::none());
+  m.def("attn_decode_fp8", &attn_decode_fp8,
+        "split-KV decode attention over the e4m3 cache (gfx950)",
+        py::arg("q"), py::arg("k8"), py::arg("k_scale"), py::arg("v8"),
+        py::arg("v_scale"), py::arg("scale"), py::arg("alibi") = py::none(),
+        py::arg("kv_lens") = py::none());
   m.def("attn_fwd_blocked", &attn_fwd_blocked,
         "blocked fwd for head_dim > 128 (hipBLASLt scores)");
   m.def("attn_bwd", &attn_bwd, "flash attention bwd (gfx950 MFMA)",

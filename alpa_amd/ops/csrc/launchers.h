@@ -149,6 +149,32 @@ hipError_t launch_attn_decode(const void* q, const void* k, const void* v,
                               const float* alibi, const int* kv_lens,
                               const int64_t* strides, hipStream_t stream);
 
+// ---- attention_decode_fp8.hip ----
+// launch_attn_decode over an e4m3 cache: k8, v8 [B,H,Skv,D] bytes with 16-
+// byte-aligned rows, k_scale, v_scale [B,H,Skv] fp32, one scale per row.
+// strides: q(3) k8(3) v8(3) o(3) k_scale(3) v_scale(3), each (batch, head,
+// seq) in elements; chunking and workspace as for launch_attn_decode
+hipError_t launch_attn_decode_fp8(const void* q, const void* k8,
+                                  const float* k_scale, const void* v8,
+                                  const float* v_scale, void* o, float* lse,
+                                  float* ws, int64_t B, int64_t H,
+                                  int64_t Skv, int64_t D, float scale,
+                                  const float* alibi, const int* kv_lens,
+                                  const int64_t* strides, hipStream_t stream);
+
+// ---- kv_cache_fp8.hip ----
+// quantize k, v [B,H,S,D] bf16 (16-byte-aligned rows) per row to e4m3 and
+// write row (b, h, s) at cache position pos_b + s of k8/v8 [B,H,max_len,D]
+// (8-byte-aligned rows) and k_scale/v_scale [B,H,max_len]; positions outside
+// [0, max_len) are skipped.  pos_kind 0: pos_b = pos_host; 1 / 2: pos_dev is
+// int32 / int64 [B].  strides: k(3) v(3) k8(3) v8(3) k_scale(3) v_scale(3)
+hipError_t launch_kv_cache_append(const void* k, const void* v, void* k8,
+                                  float* k_scale, void* v8, float* v_scale,
+                                  int64_t B, int64_t H, int64_t S, int64_t D,
+                                  int64_t max_len, int64_t pos_host,
+                                  const void* pos_dev, int pos_kind,
+                                  const int64_t* strides, hipStream_t stream);
+
 // ---- moe_route.hip ----
 // top-2 + in-block ranks (left in slot1/slot2) + per-256-token-block
 // histograms and softmax column partials, all [ceil(N/256), E]

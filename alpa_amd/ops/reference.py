@@ -182,6 +182,67 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return o.to(q.dtype), lse
 
 
+# e4m3 KV cache (csrc/kv_cache_fp8.hip, csrc/attention_decode_fp8.hip).  These
+# functions are the specification the two kernels are tested against.
+E4M3_MAX = 448.0
+
+
+def kv_quantize_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [..., d] -> (bytes [..., d] float8_e4m3fn, scale [...] fp32), every
+    row on its own: scale = amax(|x|) / 448 and bytes = e4m3_rne(x / scale),
+    both divisions in fp32, the conversion saturating at +-448.  An all-zero
+    row has scale = 1.  A row that holds a NaN or an Inf has scale = NaN and
+    the e4m3 NaN code 0x7F in every byte, so the whole row dequantizes to
+    NaN: nothing is clamped into range silently."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    bad = ~torch.isfinite(amax)
+    scale = torch.where(amax == 0, torch.ones_like(amax), amax / E4M3_MAX)
+    scale = scale.masked_fill(bad, float("nan"))
+    safe = scale.masked_fill(bad, 1.0).unsqueeze(-1)
+    y = (xf.masked_fill(bad.unsqueeze(-1), 0.0) / safe).clamp(-E4M3_MAX,
+                                                              E4M3_MAX)
+    q = y.to(torch.float8_e4m3fn)
+    q.view(torch.uint8).masked_fill_(bad.unsqueeze(-1), 0x7F)
+    return q, scale
+
+
+def kv_dequantize_rows(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The fp32 rows that (bytes, scale) of kv_quantize_rows stand for."""
+    return q.float() * scale.float().unsqueeze(-1)
+
+
+def kv_cache_append_fp8(k, v, k8, k_scale, v8, v_scale, pos) -> None:
+    """Quantize k, v [B, h, S, d] per row and write row (b, h, s) at cache
+    position pos_b + s, in place; pos an int or an int tensor [B].  A row
+    whose position is outside [0, max_len) is skipped."""
+    B, _, S, _ = k.shape
+    max_len = k8.shape[2]
+    if not torch.is_tensor(pos):
+        pos = torch.full((B,), int(pos), dtype=torch.long, device=k.device)
+    at = pos.long().view(B, 1) + torch.arange(S, device=k.device).view(1, S)
+    b_idx, s_idx = torch.nonzero((at >= 0) & (at < max_len), as_tuple=True)
+    at = at[b_idx, s_idx]
+    for x, c8, cs in ((k, k8, k_scale), (v, v8, v_scale)):
+        q, sc = kv_quantize_rows(x)
+        c8.view(torch.uint8)[b_idx, :, at] = q.view(torch.uint8)[b_idx, :,
+                                                                 s_idx]
+        cs[b_idx, :, at] = sc[b_idx, :, s_idx]
+
+
+def attention_decode_fp8(q, k8, k_scale, v8, v_scale, softmax_scale=None,
+                         alibi=None, kv_lens=None):
+    """attention_fwd (non-causal) over the dequantized cache; rows at or
+    past a slot's length are never looked at, whatever they hold."""
+    k = kv_dequantize_rows(k8, k_scale)
+    v = kv_dequantize_rows(v8, v_scale)
+    if kv_lens is not None:
+        dead = (torch.arange(k.shape[2], device=k.device).view(1, 1, -1, 1)
+                >= kv_lens.to(k.device).view(-1, 1, 1, 1))
+        k, v = k.masked_fill(dead, 0.0), v.masked_fill(dead, 0.0)
+    return attention_fwd(q, k, v, False, softmax_scale, alibi, kv_lens)
+
+
 def attention_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor,
                   v: torch.Tensor, o: torch.Tensor, lse: torch.Tensor,
                   causal: bool = True, softmax_scale: float | None = None,

@@ -28,14 +28,10 @@ class GenRequest:
     done: bool = False
 
 
-class _SlotCacheView:
-    """cache.k/v views of one slot, so the model's ordinary prefill path
-    writes straight into the shared buffer."""
-
-    def __init__(self, cache, slot: int):
-        self.k = [t[slot:slot + 1] for t in cache.k]
-        self.v = [t[slot:slot + 1] for t in cache.v]
-        self.length = 0
+def _SlotCacheView(cache, slot: int):
+    """The cache of one slot, sharing the buffers, so the model's ordinary
+    prefill path writes straight into the shared cache (bf16 or e4m3)."""
+    return cache.slots(slot, 1)
 
 
 class ContinuousBatcher:
@@ -129,12 +125,7 @@ class ContinuousBatcher:
                 "prompt too long"
             ids[j, :int(lens[j])] = r.prompt_ids.to(self.device).view(-1)
 
-        class _RunView:
-            pass
-        view = _RunView()
-        view.k = [t[s0:s0 + n] for t in self.cache.k]
-        view.v = [t[s0:s0 + n] for t in self.cache.v]
-        view.length = 0
+        view = self.cache.slots(s0, n)
         with torch.no_grad():
             logits = self.model.forward_prefill(ids, lens, view)
         toks = self.model.greedy_token(logits)

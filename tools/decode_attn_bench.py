@@ -6,6 +6,12 @@
       ext.attn_fwd_blocked on the cache sliced to the slot length, as
       forward_step does
   (b) ext.attn_decode (csrc/attention_decode.hip)
+  (c) ext.attn_decode_fp8 (csrc/attention_decode_fp8.hip) over the e4m3
+      cache that ext.kv_cache_append makes of the same k and v
+
+and, per shape and batch, the append of one token per slot at per-slot
+positions: ext.kv_cache_append (one launch, csrc/kv_cache_fp8.hip) against
+the two index_put scatters into the bf16 cache that it replaces.
 
 Shapes (heads, head_dim): (40, 128) OPT-13B, (56, 128) OPT-30B, (32, 128)
 with ALiBi BLOOM-7.1B, (24, 256) CodeGen-16B; batch 1, 8, 32; slot length
@@ -95,6 +101,13 @@ in the library: masking by kv_lens at head_dim 256 exists in the decode
 kernel only, and route (a) there is timed on a cache sliced by hand.  Its
 cost in (b) is the 15 dead chunks per (batch, head), which load nothing
 but still take 6-7 ns each to dispatch.
+
+The table above predates route (c).  With (c) the columns are: a, b, c in us;
+a/b and b/c; "spread", the largest (max - min) / median of the three routes;
+"b MB" and "c MB", what (b) and (c) have to read or write, from the shapes (c:
+1-byte K and V of the visible rows, 2 * B * H * len * D, their fp32 scales,
+2 * B * H * len * 4, and the same workspace), and the GB/s each achieves.
+That table and the append table are in docs/BENCHMARK.md, "e4m3 KV cache".
 """
 import statistics
 import sys
@@ -112,7 +125,6 @@ SHAPES = [("OPT-13B", 40, 128, False), ("OPT-30B", 56, 128, False),
 BATCHES = (1, 8, 32)
 LENGTHS = (128, 512, 2048)
 CAPACITY = 2048
-HBM_BYTES_PER_S = 6.3e12
 INFINITY_CACHE_BYTES = 256 * 2 ** 20
 
 
@@ -132,12 +144,52 @@ def spread(ts):
     return (max(ts) - min(ts)) / statistics.median(ts)
 
 
+def moved_bytes(B, H, D, n, Skv, elem, scales):
+    """What a split-KV decode kernel has to move: K and V of the visible
+    rows, their scales, and the fp32 workspace written and read once."""
+    n_chunks = -(-Skv // DECODE_ATTN_CHUNK(D))
+    live = -(-n // DECODE_ATTN_CHUNK(D))
+    ws = 0 if n_chunks == 1 else 2 * B * H * live * (D + 2) * 4
+    return 2 * B * H * n * (D * elem + (4 if scales else 0)) + ws
+
+
+def bench_append(ext, name, H, D, B, kcap, vcap, cache8):
+    """One token per slot at per-slot positions: the fused append against
+    the two scatters of DecoderBlock._attn."""
+    g = torch.Generator(device="cuda").manual_seed(1)
+    qkv = torch.randn(B, 1, H, 3, D, device="cuda", generator=g).bfloat16()
+    k, v = (qkv[:, :, :, i].permute(0, 2, 1, 3) for i in (1, 2))
+    pos = torch.randint(0, CAPACITY, (B,), device="cuda", generator=g)
+    bidx = torch.arange(B, device="cuda")
+
+    def scatters():
+        kcap[bidx, :, pos] = k[:, :, 0]
+        vcap[bidx, :, pos] = v[:, :, 0]
+
+    def fused():
+        ext.kv_cache_append(k, v, *cache8, 0, pos)
+
+    cases = [("scatter", scatters), ("fused", fused)]
+    for _, fn in cases:
+        timed(fn, WARMUP)
+    times = {c: [] for c, _ in cases}
+    for _ in range(ROUNDS):
+        for c, fn in cases:
+            times[c].append(timed(fn))
+    s_, f_ = (statistics.median(times[c]) for c in ("scatter", "fused"))
+    return (f"append {name:12s} {H:3d} {D:3d} {B:3d} {s_:8.1f} {f_:8.1f} "
+            f"{s_ / f_:6.2f} "
+            f"{max(spread(times['scatter']), spread(times['fused'])):6.2f}")
+
+
 def main():
     assert torch.cuda.is_available(), "needs a GPU"
     ext = hip_ops()
     print(f"{'model':12s} {'H':>3s} {'D':>3s} {'B':>3s} {'len':>5s} "
-          f"{'Skv':>5s} {'a us':>8s} {'b us':>8s} {'a/b':>6s} "
-          f"{'spread':>6s} {'GB/s':>7s} {'%HBM':>5s} {'max|a-b|':>9s}")
+          f"{'Skv':>5s} {'a us':>8s} {'b us':>8s} {'c us':>8s} {'a/b':>6s} "
+          f"{'b/c':>6s} {'spread':>6s} {'b MB':>7s} {'b GB/s':>7s} "
+          f"{'c MB':>7s} {'c GB/s':>7s} {'max|a-b|':>9s} {'max|b-c|':>9s}")
+    append_rows = []
     for name, H, D, alibi in SHAPES:
         slopes = alibi_slopes(H).cuda() if alibi else None
         scale = D ** -0.5
@@ -148,13 +200,19 @@ def main():
                                generator=g).bfloat16()
             vcap = torch.randn(B, H, CAPACITY, D, device="cuda",
                                generator=g).bfloat16()
+            cap8 = [torch.zeros(B, H, CAPACITY, D, dtype=torch.uint8,
+                                device="cuda").view(torch.float8_e4m3fn),
+                    torch.zeros(B, H, CAPACITY, device="cuda")]
+            cap8 += [t.clone() for t in cap8]
+            ext.kv_cache_append(kcap, vcap, *cap8, 0, None)
             for n in LENGTHS:
                 for Skv in sorted({n, CAPACITY}):
                     if Skv == CAPACITY:
-                        k, v = kcap, vcap
+                        k, v, c8 = kcap, vcap, cap8
                     else:
                         k = kcap[:, :, :Skv].contiguous()
                         v = vcap[:, :, :Skv].contiguous()
+                        c8 = [t[:, :, :Skv].contiguous() for t in cap8]
                     lens = torch.full((B,), n, dtype=torch.int32,
                                       device="cuda")
 
@@ -171,30 +229,38 @@ def main():
                         return ext.attn_decode(q, k, v, scale, slopes,
                                                lens)[0]
 
-                    diff = (path_a().float() - path_b().float()) \
-                        .abs().max().item()
-                    cases = [("a", path_a), ("b", path_b)]
+                    def path_c():
+                        return ext.attn_decode_fp8(q, *c8, scale, slopes,
+                                                   lens)[0]
+
+                    ob = path_b().float()
+                    diff = (path_a().float() - ob).abs().max().item()
+                    diff8 = (path_c().float() - ob).abs().max().item()
+                    cases = [("a", path_a), ("b", path_b), ("c", path_c)]
                     for _, fn in cases:
                         timed(fn, WARMUP)
                     times = {c: [] for c, _ in cases}
                     for _ in range(ROUNDS):
                         for c, fn in cases:
                             times[c].append(timed(fn))
-                    a = statistics.median(times["a"])
-                    b = statistics.median(times["b"])
-                    n_chunks = -(-Skv // DECODE_ATTN_CHUNK(D))
-                    live = -(-n // DECODE_ATTN_CHUNK(D))
-                    ws = 0 if n_chunks == 1 else 2 * B * H * live * (D + 2) * 4
-                    moved = 2 * B * H * n * D * 2 + ws
-                    rate = moved / (b * 1e-6)
-                    tag = " cache" if moved < INFINITY_CACHE_BYTES else ""
+                    a, b, c = (statistics.median(times[x]) for x in "abc")
+                    mb = moved_bytes(B, H, D, n, Skv, 2, False)
+                    mc = moved_bytes(B, H, D, n, Skv, 1, True)
+                    tag = " cache" if mb < INFINITY_CACHE_BYTES else ""
                     print(f"{name:12s} {H:3d} {D:3d} {B:3d} {n:5d} {Skv:5d} "
-                          f"{a:8.1f} {b:8.1f} {a / b:6.2f} "
-                          f"{max(spread(times['a']), spread(times['b'])):6.2f}"
-                          f" {rate / 1e9:7.0f} {100 * rate / HBM_BYTES_PER_S:5.1f}"
-                          f" {diff:9.2g}{tag}")
-            del q, kcap, vcap
+                          f"{a:8.1f} {b:8.1f} {c:8.1f} {a / b:6.2f} "
+                          f"{b / c:6.2f} "
+                          f"{max(spread(t) for t in times.values()):6.2f} "
+                          f"{mb / 1e6:7.1f} {mb / (b * 1e3):7.0f} "
+                          f"{mc / 1e6:7.1f} {mc / (c * 1e3):7.0f} "
+                          f"{diff:9.2g} {diff8:9.2g}{tag}", flush=True)
+            append_rows.append(bench_append(ext, name, H, D, B, kcap, vcap,
+                                            cap8))
+            del q, kcap, vcap, cap8
             torch.cuda.empty_cache()
+    print(f"\nappend {'model':12s} {'H':>3s} {'D':>3s} {'B':>3s} "
+          f"{'2 scat':>8s} {'fused':>8s} {'s/f':>6s} {'spread':>6s}  (us)")
+    print("\n".join(append_rows))
 
 
 if __name__ == "__main__":
