@@ -2,13 +2,14 @@
 
 One block (packed qkv, KV-cache write, attention, MLP), one model scaffold
 (embedding, blocks, final norm, vocab-parallel head) and one set of serving
-entry points: ``forward_step`` (prefill / single-token decode at a common
-position), ``forward_prefill`` (right-padded batch), ``forward_decode``
+entry points: ``forward_step`` (prefill, a further chunk of tokens or one
+token at a common position), ``forward_prefill`` (right-padded batch), ``forward_decode``
 (one token per slot at per-slot positions, continuous batching) and the
 hipGraph-captured decode loop.  A family (opt.py, bloom.py, codegen.py)
 supplies its config, its embedding and what its attention needs per call
 (ALiBi slopes, a rotary transform); everything that reaches
-``ops.flash_attention`` / ``ops.flash_attention_varlen`` is here.
+``ops.flash_attention`` / ``ops.flash_attention_varlen`` /
+``ops.flash_attention_chunk`` is here.
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ class KVCache:
     fp8 (global_config.kv_cache_fp8): k and v hold float8_e4m3fn bytes and
     k_scale, v_scale [B, heads/tp, max_len] one fp32 scale per cached row
     (ops.kv_cache_append_fp8 writes them, ops.flash_attention_decode_fp8
-    reads them); otherwise k_scale and v_scale are None."""
+    and ops.flash_attention_chunk_fp8 read them); otherwise k_scale and v_scale are None."""
 
     def __init__(self, cfg, num_layers: int, batch: int,
                  heads_per_rank: int, dtype, device,
@@ -153,11 +154,16 @@ class DecoderBlock(nn.Module):
             total = pos + S
             cache_k[:, :, pos:total] = k
             cache_v[:, :, pos:total] = v
-            # a single new position sees the whole cache; a chunk with
-            # history would need a causal offset (forward_step refuses it)
-            o = ops.flash_attention(q, cache_k[:, :, :total],
-                                    cache_v[:, :, :total], causal=S > 1,
-                                    alibi_slopes=slopes)
+            if pos > 0 and S > 1:
+                # a chunk with history: causal at the end of the cache
+                o = ops.flash_attention_chunk(q, cache_k[:, :, :total],
+                                              cache_v[:, :, :total],
+                                              alibi_slopes=slopes)
+            else:
+                # a single new position sees the whole cache
+                o = ops.flash_attention(q, cache_k[:, :, :total],
+                                        cache_v[:, :, :total], causal=S > 1,
+                                        alibi_slopes=slopes)
         else:
             assert S == 1
             bidx = torch.arange(B, device=x.device)
@@ -173,15 +179,21 @@ class DecoderBlock(nn.Module):
         """The cached branches of _attn over an e4m3 cache: cache_k and
         cache_v are (bytes, scales).  Prefill attends over the fresh bf16
         k/v, which is all there is to see at pos == 0, and then appends;
-        a single-token step appends first and reads the cache through the
-        e4m3 decode kernel with kv_lens = pos + 1."""
+        a chunk with history appends first and reads the cache through the
+        e4m3 chunk kernel; a single-token step appends first and reads the
+        cache through the e4m3 decode kernel with kv_lens = pos + 1."""
         (k8, ks), (v8, vs) = cache_k, cache_v
         B, S = q.shape[0], q.shape[2]
         if S > 1:
-            assert isinstance(pos, int) and pos == 0
-            ops.kv_cache_append_fp8(k, v, k8, ks, v8, vs, 0)
-            return ops.flash_attention(q, k.contiguous(), v.contiguous(),
-                                       causal=True, alibi_slopes=slopes)
+            assert isinstance(pos, int)
+            ops.kv_cache_append_fp8(k, v, k8, ks, v8, vs, pos)
+            if pos == 0:
+                return ops.flash_attention(q, k.contiguous(), v.contiguous(),
+                                           causal=True, alibi_slopes=slopes)
+            total = pos + S
+            return ops.flash_attention_chunk_fp8(
+                q, k8[:, :, :total], ks[:, :, :total], v8[:, :, :total],
+                vs[:, :, :total], alibi_slopes=slopes)
         ops.kv_cache_append_fp8(k, v, k8, ks, v8, vs, pos)
         if isinstance(pos, int):
             total, lens = pos + 1, None
@@ -271,13 +283,13 @@ class CachedDecoder(nn.Module, GenerationMixin):
 
     def forward_step(self, ids: torch.Tensor, cache: KVCache
                      ) -> torch.Tensor:
-        """ids [B, S] (prefill) or [B, 1] (decode). Returns last-position
+        """ids [B, S]: the S tokens at positions cache.length ..
+        cache.length + S - 1 of every slot: a whole prompt, a further chunk
+        of one (chunked prefill, draft verification, a multi-token turn;
+        ops.flash_attention_chunk) or one token.  Returns last-position
         logits [B, vocab/tp]."""
         S = ids.shape[1]
         pos = cache.length
-        # chunked decode with history would need a causal-offset mask in the
-        # kernel; prefill (pos==0) and single-token decode cover serving
-        assert pos == 0 or S == 1, "chunked decode with history unsupported"
         x = self._run_blocks(self._embed(ids, pos), cache, pos)
         cache.length += S
         return self.lm_head(self.ln_f(x[:, -1:]))[:, 0]

@@ -17,6 +17,10 @@ single-token queries, which flash_attention and flash_attention_varlen use
 for every decode step.  kv_cache_append_fp8 and flash_attention_decode_fp8
 are the write and the read side of the e4m3 KV cache (one fp32 scale per
 cached row), which global_config.kv_cache_fp8 turns on in the decoders.
+flash_attention_chunk and flash_attention_chunk_fp8 are the split-KV MFMA
+kernel for several query rows over a cache that already holds them (chunked
+prefill, draft verification, a multi-token turn), causal at the end of the
+cache.
 
 Kernel-level contract mirrors the reference's compiled-HLO op inventory
 (GEMM+epilogue, attention, LayerNorm, fused Adam,
@@ -39,6 +43,8 @@ __all__ = [
     "flash_attention_qkv", "flash_attention_decode", "decode_attn_ok",
     "DECODE_ATTN_CHUNK", "kv_cache_append_fp8",
     "flash_attention_decode_fp8", "decode_attn_fp8_ok",
+    "flash_attention_chunk", "chunk_attn_ok", "flash_attention_chunk_fp8",
+    "chunk_attn_fp8_ok",
     "softmax_cross_entropy",
     "softmax_cross_entropy_partial", "softmax_cross_entropy_combine",
     "softmax_cross_entropy_shard_bwd", "vocab_ce_fused_ok", "fused_adamw",
@@ -353,19 +359,21 @@ def _rows_aligned16(t: torch.Tensor) -> bool:
         t.shape[i] <= 1 or t.stride(i) % 8 == 0 for i in range(3))
 
 
-def decode_attn_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
-    """Envelope of the split-KV decode attention kernel
-    (csrc/attention_decode.hip; the binding checks the same): bf16 on the
-    GPU, q [B, h, 1, d] and k, v [B, h, Skv, d] views with a contiguous
+def chunk_attn_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
+    """Envelope of the split-KV kernels over a bf16 cache
+    (csrc/attention_chunk.hip, and with one query row
+    csrc/attention_decode.hip; the bindings check the same): bf16 on the
+    GPU, q [B, h, Sq, d] and k, v [B, h, Skv, d] views with a contiguous
     head dim, d a multiple of 16 up to 256, and every row 16-byte aligned
     (aligned base, batch/head/seq strides multiples of 8 elements) for the
-    16-byte loads."""
+    16-byte loads.  Sq is free: flash_attention_chunk cuts it into launches
+    of at most 64 rows."""
     for t in (q, k, v):
         if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
                 and t.stride(3) == 1):
             return False
     D = q.shape[3]
-    if q.shape[2] != 1 or D % 16 != 0 or not 16 <= D <= 256:
+    if q.shape[2] < 1 or D % 16 != 0 or not 16 <= D <= 256:
         return False
     if k.shape != v.shape or k.shape[:2] != q.shape[:2] or k.shape[3] != D \
             or q.shape[0] * q.shape[1] > 65535:
@@ -373,6 +381,13 @@ def decode_attn_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
     if not all(_rows_aligned16(t) for t in (q, k, v)):
         return False
     return use_hip(q)
+
+
+def decode_attn_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
+    """Envelope of the split-KV decode attention kernel
+    (csrc/attention_decode.hip): chunk_attn_ok with exactly one query row,
+    q [B, h, 1, d]."""
+    return q.dim() == 4 and q.shape[2] == 1 and chunk_attn_ok(q, k, v)
 
 
 def _decode_attn_routed(q, k, v) -> bool:
@@ -432,12 +447,13 @@ def _kv8_ok(c8: torch.Tensor, cs: torch.Tensor, first: torch.Tensor,
             and cs.dtype == torch.float32 and cs.shape == c8.shape[:3])
 
 
-def decode_attn_fp8_ok(q: torch.Tensor, k8: torch.Tensor,
-                       k_scale: torch.Tensor, v8: torch.Tensor,
-                       v_scale: torch.Tensor) -> bool:
-    """Envelope of the e4m3-cache decode kernel
-    (csrc/attention_decode_fp8.hip; the binding checks the same).  It is
-    decode_attn_ok with the cache in bytes: q bf16 [B, h, 1, d] on the GPU,
+def chunk_attn_fp8_ok(q: torch.Tensor, k8: torch.Tensor,
+                      k_scale: torch.Tensor, v8: torch.Tensor,
+                      v_scale: torch.Tensor) -> bool:
+    """Envelope of the split-KV kernels over an e4m3 cache
+    (csrc/attention_chunk.hip, and with one query row
+    csrc/attention_decode_fp8.hip; the bindings check the same).  It is
+    chunk_attn_ok with the cache in bytes: q bf16 [B, h, Sq, d] on the GPU,
     k8, v8 [B, h, Skv, d] float8_e4m3fn views with a contiguous head dim, d
     a multiple of 16 up to 256, every q row and every cache row 16-byte
     aligned; plus k_scale, v_scale fp32 [B, h, Skv] on the same device (any
@@ -446,7 +462,7 @@ def decode_attn_fp8_ok(q: torch.Tensor, k8: torch.Tensor,
             and q.stride(3) == 1 and _rows_aligned16(q)):
         return False
     D = q.shape[3]
-    if q.shape[2] != 1 or D % 16 != 0 or not 16 <= D <= 256 \
+    if q.shape[2] < 1 or D % 16 != 0 or not 16 <= D <= 256 \
             or q.shape[0] * q.shape[1] > 65535:
         return False
     if not (_kv8_ok(k8, k_scale, q, 16) and _kv8_ok(v8, v_scale, q, 16)):
@@ -455,6 +471,16 @@ def decode_attn_fp8_ok(q: torch.Tensor, k8: torch.Tensor,
             or k8.shape[3] != D:
         return False
     return use_hip(q)
+
+
+def decode_attn_fp8_ok(q: torch.Tensor, k8: torch.Tensor,
+                       k_scale: torch.Tensor, v8: torch.Tensor,
+                       v_scale: torch.Tensor) -> bool:
+    """Envelope of the e4m3-cache decode kernel
+    (csrc/attention_decode_fp8.hip): chunk_attn_fp8_ok with exactly one
+    query row, q [B, h, 1, d]."""
+    return q.dim() == 4 and q.shape[2] == 1 and \
+        chunk_attn_fp8_ok(q, k8, k_scale, v8, v_scale)
 
 
 def _kv_append_ok(k, v, k8, k_scale, v8, v_scale, pos) -> bool:
@@ -545,6 +571,95 @@ def flash_attention_decode_fp8(q: torch.Tensor, k8: torch.Tensor,
     o, _ = ref.attention_decode_fp8(q, k8, k_scale, v8, v_scale, scale,
                                     alibi_slopes, lens)
     return o
+
+
+# query rows per launch of csrc/attention_chunk.hip (its QT = 4 instantiation)
+_CHUNK_ATTN_MAX_ROWS = 64
+
+
+def _chunk_pieces(Sq: int, Skv: int, lens: Optional[torch.Tensor]):
+    """Cut Sq query rows into launches of at most 64: piece [a, b) sits
+    Sq - b rows before the end of its slot, so it runs with the slot's
+    length less Sq - b.  Yields (a, b, cache rows to pass, lengths): with
+    lengths they are computed on the device and the whole view is passed;
+    without, the view is cut instead.  No host read either way."""
+    for a in range(0, Sq, _CHUNK_ATTN_MAX_ROWS):
+        b = min(a + _CHUNK_ATTN_MAX_ROWS, Sq)
+        if lens is None:
+            yield a, b, max(Skv - (Sq - b), 0), None
+        else:
+            yield a, b, Skv, (lens if b == Sq else lens - (Sq - b))
+
+
+@torch.no_grad()
+def flash_attention_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                          kv_lens: Optional[torch.Tensor] = None,
+                          scale: Optional[float] = None,
+                          alibi_slopes: Optional[torch.Tensor] = None
+                          ) -> torch.Tensor:
+    """Attention of Sq new query rows over a cache that already holds them:
+    q [B, h, Sq, d]; k, v [B, h, Skv, d], of which slot b uses the first
+    len_b = kv_lens[b] (default Skv) rows, the last Sq of them being the new
+    ones.  Query row i sits at position len_b - Sq + i and sees keys up to
+    and including that position (a causal mask aligned with the end of the
+    cache); a row at a negative position gives o = 0.  Returns o
+    [B, h, Sq, d].  Inference only; any Sq >= 1.
+
+    Inside chunk_attn_ok this is the split-KV MFMA kernel for gfx950
+    (csrc/attention_chunk.hip): one workgroup per DECODE_ATTN_CHUNK(d) keys
+    takes up to 64 query rows through QK^T, a one-tile softmax and PV on
+    matrix instructions, and a second launch merges the chunks; longer q
+    runs as pieces of at most 64 rows.  It reads strided views in place,
+    never loads a row at or past a slot's length, rounds P to bf16 once, and
+    a slot's output bits depend only on that slot's own q, visible k/v
+    rows, length, Sq, d, scale and slope.  kv_lens may live on the device:
+    there is no host read, so the call can be captured in a graph.  On CPU
+    or outside the envelope it is reference.attention_chunk."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    lens = None if kv_lens is None else kv_lens.to(dtype=torch.int32)
+    if not chunk_attn_ok(q, k, v):
+        return ref.attention_chunk(q, k, v, scale, alibi_slopes, lens)[0]
+    Sq, Skv = q.shape[2], k.shape[2]
+    outs = [hip_ops().attn_chunk(
+        q[:, :, a:b], k[:, :, :n], v[:, :, :n], scale, alibi_slopes,
+        None if ln is None else ln.contiguous())[0]
+        for a, b, n, ln in _chunk_pieces(Sq, Skv, lens)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=2)
+
+
+@torch.no_grad()
+def flash_attention_chunk_fp8(q: torch.Tensor, k8: torch.Tensor,
+                              k_scale: torch.Tensor, v8: torch.Tensor,
+                              v_scale: torch.Tensor,
+                              kv_lens: Optional[torch.Tensor] = None,
+                              scale: Optional[float] = None,
+                              alibi_slopes: Optional[torch.Tensor] = None
+                              ) -> torch.Tensor:
+    """flash_attention_chunk over the e4m3 cache that kv_cache_append_fp8
+    writes: k8, v8 [B, h, Skv, d] with per-row scales [B, h, Skv]; returns
+    o [B, h, Sq, d] in q's dtype.  Inference only.
+
+    Inside chunk_attn_fp8_ok this is the e4m3 instantiation of the same
+    kernel: K bytes become bf16 in registers and k_scale[row] multiplies the
+    fp32 score; V bytes become bf16 while they are staged and v_scale[row]
+    is folded into p in fp32 before its one rounding to bf16.  Rows at or
+    past a slot's length are never loaded, scales included; a visible row
+    with a NaN scale gives a NaN output.  On CPU or outside the envelope it
+    is reference.attention_chunk_fp8."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    lens = None if kv_lens is None else kv_lens.to(dtype=torch.int32)
+    if not chunk_attn_fp8_ok(q, k8, k_scale, v8, v_scale):
+        return ref.attention_chunk_fp8(q, k8, k_scale, v8, v_scale, scale,
+                                       alibi_slopes, lens)[0]
+    Sq, Skv = q.shape[2], k8.shape[2]
+    outs = [hip_ops().attn_chunk_fp8(
+        q[:, :, a:b], k8[:, :, :n], k_scale[:, :, :n], v8[:, :, :n],
+        v_scale[:, :, :n], scale, alibi_slopes,
+        None if ln is None else ln.contiguous())[0]
+        for a, b, n, ln in _chunk_pieces(Sq, Skv, lens)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=2)
 
 
 @torch.no_grad()

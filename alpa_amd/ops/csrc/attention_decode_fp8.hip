@@ -59,12 +59,6 @@ __device__ __forceinline__ void unpack_e4m3x16(u32x4 x, float* f) {
   }
 }
 
-// element strides of k_scale and v_scale [B, H, Skv]
-struct ScaleStrides {
-  int64_t kb, kh, ks;
-  int64_t vb, vh, vs;
-};
-
 // Dp: head dim padded to 64/128/256; CH: keys per chunk; AL: ALiBi bias.
 // st: q and o in bf16 elements, k8 and v8 in bytes.  ws as in
 // attention_decode.hip; unused when gridDim.x == 1.

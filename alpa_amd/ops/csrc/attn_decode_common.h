@@ -2,7 +2,9 @@
 // bf16 cache; attention_decode_fp8.hip: e4m3 cache): the launch geometry, the
 // chunk size, the slot length, the one place a row is normalised and the
 // combine kernel.  Both partial kernels write the same fp32 workspace, so
-// one combine serves both.
+// one combine serves both.  The chunk kernel for several query rows
+// (attention_chunk.hip) takes the geometry, the chunk size, the slot length
+// and the normalisation from here and has a combine of its own.
 #pragma once
 
 #include "attn_strides.h"
@@ -17,6 +19,12 @@
 template <int Dp>
 struct DecodeChunk {
   static constexpr int value = 128;
+};
+
+// element strides of the k_scale and v_scale [B, H, Skv] of an e4m3 cache
+struct ScaleStrides {
+  int64_t kb, kh, ks;
+  int64_t vb, vh, vs;
 };
 
 // The one place a row is normalised, shared by the combine kernel and the

@@ -766,6 +766,84 @@ std::vector<at::Tensor> attn_decode_fp8(
   return {o, lse};
 }
 
+// Chunk attention (attention_chunk.hip): 1 <= Sq <= 64 query rows per
+// (batch, head) over a cache that already holds them; row i sits at position
+// len_b - Sq + i and sees keys j <= that (len_b = kv_lens[b] or Skv).
+// Operands as for attn_decode.  Returns (o [B,H,Sq,D] bf16, lse [B,H,Sq]).
+std::vector<at::Tensor> attn_chunk(const at::Tensor& q, const at::Tensor& k,
+                                   const at::Tensor& v, double scale,
+                                   const c10::optional<at::Tensor>& alibi =
+                                       c10::nullopt,
+                                   const c10::optional<at::Tensor>& kv_lens =
+                                       c10::nullopt) {
+  check_bhsd(q, "q", -1, -1, -1, -1, q);
+  const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2), D = q.size(3);
+  TORCH_CHECK(Sq >= 1 && Sq <= 64, "q must hold 1 to 64 query rows per head, "
+              "got ", Sq);
+  check_bhsd(k, "k", B, H, -1, D, q);
+  const int64_t Skv = k.size(2);
+  check_bhsd(v, "v", B, H, Skv, D, q);
+  TORCH_CHECK(D > 0 && D % 16 == 0 && D <= 256,
+              "head_dim must be a multiple of 16 up to 256, got ", D);
+  TORCH_CHECK(B * H <= 65535, "q: at most 65535 (batch, head) pairs, got ",
+              B * H);
+  if (given(alibi)) check_vec(*alibi, "alibi", at::kFloat, H, q);
+  if (given(kv_lens)) check_vec(*kv_lens, "kv_lens", at::kInt, B, q);
+  check_rows_aligned16(q, "q");
+  check_rows_aligned16(k, "k");
+  check_rows_aligned16(v, "v");
+  auto f32 = q.options().dtype(at::kFloat);
+  auto o = at::empty({B, H, Sq, D}, q.options());
+  auto lse = at::empty({B, H, Sq}, f32);
+  if (B * H == 0) return {o, lse};
+  auto ws = at::empty({attn_chunk_workspace_floats(B, H, Sq, Skv, D)}, f32);
+  const auto strides = bhs_strides(q, k, v, o);
+  HIP_OK(launch_attn_chunk(q.const_data_ptr(), k.const_data_ptr(),
+                           v.const_data_ptr(), o.mutable_data_ptr(),
+                           (float*)lse.mutable_data_ptr(),
+                           (float*)ws.mutable_data_ptr(), B, H, Sq, Skv, D,
+                           (float)scale, (const float*)opt_ptr(alibi),
+                           (const int*)opt_ptr(kv_lens), strides.data(),
+                           cur_stream()));
+  return {o, lse};
+}
+
+// attn_chunk over the e4m3 cache; operands as for attn_decode_fp8.
+std::vector<at::Tensor> attn_chunk_fp8(
+    const at::Tensor& q, const at::Tensor& k8, const at::Tensor& k_scale,
+    const at::Tensor& v8, const at::Tensor& v_scale, double scale,
+    const c10::optional<at::Tensor>& alibi = c10::nullopt,
+    const c10::optional<at::Tensor>& kv_lens = c10::nullopt) {
+  check_bhsd(q, "q", -1, -1, -1, -1, q);
+  const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2), D = q.size(3);
+  TORCH_CHECK(Sq >= 1 && Sq <= 64, "q must hold 1 to 64 query rows per head, "
+              "got ", Sq);
+  TORCH_CHECK(D > 0 && D % 16 == 0 && D <= 256,
+              "head_dim must be a multiple of 16 up to 256, got ", D);
+  TORCH_CHECK(B * H <= 65535, "q: at most 65535 (batch, head) pairs, got ",
+              B * H);
+  check_rows_aligned16(q, "q");
+  check_kv8(k8, k_scale, "k8", "k_scale", B, H, -1, D, 16, q);
+  const int64_t Skv = k8.size(2);
+  check_kv8(v8, v_scale, "v8", "v_scale", B, H, Skv, D, 16, q);
+  if (given(alibi)) check_vec(*alibi, "alibi", at::kFloat, H, q);
+  if (given(kv_lens)) check_vec(*kv_lens, "kv_lens", at::kInt, B, q);
+  auto f32 = q.options().dtype(at::kFloat);
+  auto o = at::empty({B, H, Sq, D}, q.options());
+  auto lse = at::empty({B, H, Sq}, f32);
+  if (B * H == 0) return {o, lse};
+  auto ws = at::empty({attn_chunk_workspace_floats(B, H, Sq, Skv, D)}, f32);
+  const auto strides = bhs_strides(q, k8, v8, o, k_scale, v_scale);
+  HIP_OK(launch_attn_chunk_fp8(
+      q.const_data_ptr(), k8.const_data_ptr(),
+      (const float*)k_scale.const_data_ptr(), v8.const_data_ptr(),
+      (const float*)v_scale.const_data_ptr(), o.mutable_data_ptr(),
+      (float*)lse.mutable_data_ptr(), (float*)ws.mutable_data_ptr(), B, H,
+      Sq, Skv, D, (float)scale, (const float*)opt_ptr(alibi),
+      (const int*)opt_ptr(kv_lens), strides.data(), cur_stream()));
+  return {o, lse};
+}
+
 // Blocked attention forward for head_dim > 128 (the fused kernel tiles
 // head_dim in registers up to 128): q-block loop, scores via bf16
 // hipBLASLt GEMMs, fp32 softmax, never materializes more than one
@@ -1196,7 +1274,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // 9: layer_norm_bwd, add_layer_norm_bwd, bias_gelu_bwd and colsum_bf16
   // take an optional out_dtype (fp32 or bf16) for the vectors they reduce
   // 10: kv_cache_append and attn_decode_fp8 added (e4m3 KV cache)
-  m.attr("ABI_VERSION") = 10;
+  // 11: attn_chunk and attn_chunk_fp8 added (query chunks over a KV cache)
+  m.attr("ABI_VERSION") = 11;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)",
         py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),
@@ -1260,6 +1339,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "split-KV decode attention over the e4m3 cache (gfx950)",
         py::arg("q"), py::arg("k8"), py::arg("k_scale"), py::arg("v8"),
         py::arg("v_scale"), py::arg("scale"), py::arg("alibi") = py::none(),
+        py::arg("kv_lens") = py::none());
+  m.def("attn_chunk", &attn_chunk,
+        "split-KV MFMA attention, 1..64 query rows over a cache (gfx950)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+        py::arg("alibi") = py::none(), py::arg("kv_lens") = py::none());
+  m.def("attn_chunk_fp8", &attn_chunk_fp8,
+        "attn_chunk over the e4m3 cache (gfx950)", py::arg("q"),
+        py::arg("k8"), py::arg("k_scale"), py::arg("v8"), py::arg("v_scale"),
+        py::arg("scale"), py::arg("alibi") = py::none(),
         py::arg("kv_lens") = py::none());
   m.def("attn_fwd_blocked", &attn_fwd_blocked,
         "blocked fwd for head_dim > 128 (hipBLASLt scores)");

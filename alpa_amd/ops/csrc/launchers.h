@@ -162,6 +162,28 @@ hipError_t launch_attn_decode_fp8(const void* q, const void* k8,
                                   const float* alibi, const int* kv_lens,
                                   const int64_t* strides, hipStream_t stream);
 
+// ---- attention_chunk.hip ----
+// 1 <= Sq <= 64 query rows per (batch, head) over a cache that already holds
+// them: row i sits at position len_b - Sq + i and sees keys j <= that
+// (len_b = kv_lens[b] clamped to [0, Skv], or Skv).  Operands, strides and
+// chunking as for launch_attn_decode / launch_attn_decode_fp8; o [B,H,Sq,D]
+// and lse [B*H*Sq] are written for every row
+int64_t attn_chunk_workspace_floats(int64_t B, int64_t H, int64_t Sq,
+                                    int64_t Skv, int64_t D);
+hipError_t launch_attn_chunk(const void* q, const void* k, const void* v,
+                             void* o, float* lse, float* ws, int64_t B,
+                             int64_t H, int64_t Sq, int64_t Skv, int64_t D,
+                             float scale, const float* alibi,
+                             const int* kv_lens, const int64_t* strides,
+                             hipStream_t stream);
+hipError_t launch_attn_chunk_fp8(const void* q, const void* k8,
+                                 const float* k_scale, const void* v8,
+                                 const float* v_scale, void* o, float* lse,
+                                 float* ws, int64_t B, int64_t H, int64_t Sq,
+                                 int64_t Skv, int64_t D, float scale,
+                                 const float* alibi, const int* kv_lens,
+                                 const int64_t* strides, hipStream_t stream);
+
 // ---- kv_cache_fp8.hip ----
 // quantize k, v [B,H,S,D] bf16 (16-byte-aligned rows) per row to e4m3 and
 // write row (b, h, s) at cache position pos_b + s of k8/v8 [B,H,max_len,D]

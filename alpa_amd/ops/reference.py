@@ -243,6 +243,46 @@ def attention_decode_fp8(q, k8, k_scale, v8, v_scale, softmax_scale=None,
     return attention_fwd(q, k, v, False, softmax_scale, alibi, kv_lens)
 
 
+def attention_chunk(q, k, v, softmax_scale=None, alibi=None, kv_lens=None):
+    """Sq query rows over a cache that already holds them: q [B, Hh, Sq, D],
+    k, v [B, Hh, Skv, D], len_b = kv_lens[b] clamped to [0, Skv] (Skv without
+    lengths).  Row i of slot b sits at position p = len_b - Sq + i and sees
+    keys j <= p (a causal mask aligned bottom-right); ALiBi adds
+    slope * (j - p).  A row with p < 0 gives o = 0, lse = -inf.  Rows of k
+    and v at or past len_b are never looked at.  Returns (o, lse [B,Hh,Sq])
+    in fp32 math."""
+    B, Hh, Sq, D = q.shape
+    Skv = k.shape[2]
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    if kv_lens is None:
+        lens = torch.full((B,), Skv, dtype=torch.long, device=q.device)
+    else:
+        lens = kv_lens.to(q.device).long().clamp(0, Skv)
+    kpos = torch.arange(Skv, device=q.device).view(1, 1, 1, Skv)
+    pos = lens.view(B, 1, 1, 1) - Sq + \
+        torch.arange(Sq, device=q.device).view(1, 1, Sq, 1)
+    dead = (kpos >= lens.view(B, 1, 1, 1)).view(B, 1, Skv, 1)
+    kf, vf = _up(k).masked_fill(dead, 0.0), _up(v).masked_fill(dead, 0.0)
+    s = torch.matmul(_up(q), kf.transpose(-1, -2)) * scale
+    if alibi is not None:
+        s = s + alibi.float().view(1, Hh, 1, 1) * (kpos - pos).float()
+    s = s.masked_fill(kpos > pos, float("-inf"))
+    m = s.max(dim=-1, keepdim=True).values
+    p = torch.exp(s - m.masked_fill(m == float("-inf"), 0.0))
+    l = p.sum(dim=-1, keepdim=True)
+    o = torch.matmul(p / l.masked_fill(l == 0, 1.0), vf)
+    lse = (m + torch.log(l)).squeeze(-1)
+    return o.to(q.dtype), lse
+
+
+def attention_chunk_fp8(q, k8, k_scale, v8, v_scale, softmax_scale=None,
+                        alibi=None, kv_lens=None):
+    """attention_chunk over the dequantized cache."""
+    return attention_chunk(q, kv_dequantize_rows(k8, k_scale),
+                           kv_dequantize_rows(v8, v_scale), softmax_scale,
+                           alibi, kv_lens)
+
+
 def attention_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor,
                   v: torch.Tensor, o: torch.Tensor, lse: torch.Tensor,
                   causal: bool = True, softmax_scale: float | None = None,

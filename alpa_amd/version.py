@@ -14,8 +14,9 @@ __version__ = "0.1.0"
 #: minimum extension ABI this Python tree can drive (9: the backward entries
 #: of LayerNorm, bias+GeLU and the bias column sum take the out_dtype that
 #: every autograd function passes; 10: kv_cache_append and attn_decode_fp8,
-#: the e4m3 KV cache)
-MIN_HIP_OPS_ABI = 10
+#: the e4m3 KV cache; 11: attn_chunk and attn_chunk_fp8, query chunks over a
+#: KV cache)
+MIN_HIP_OPS_ABI = 11
 
 
 def check_hip_ops_version() -> int:
