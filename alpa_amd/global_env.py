@@ -66,6 +66,26 @@ class GlobalConfig:
     skinny_gemm: str = field(
         default_factory=lambda: os.environ.get("ALPA_AMD_SKINNY",
                                                "auto"))
+    #: MXFP4 weight-only decode GEMMs: ops.skinny_linear packs every
+    #: module that is not _fp8_exclude (so not the LM head) as e2m1
+    #: nibbles with one e8m0 scale per 32 k (4.25 bits a weight) and runs
+    #: ops/csrc/skinny_fp4.hip (up to 8 tokens) or skinny_mfma_fp4.hip
+    #: (9..64); activations stay bf16 and the nibbles are dequantized
+    #: exactly in registers, so the only error is the quantizer's.  It
+    #: goes before fp8_gemm on the skinny path only: prefill and training
+    #: are untouched.  K % 256 == 0 at every token count.  In skinny_gemm
+    #: "auto" it follows the e4m3 rules above (the hidden >= 7168
+    #: exception, the 9..64-token tiers).  Measured (tools/skinny_bench.py,
+    #: docs/BENCHMARK.md, "MXFP4 weight-only kernels", four hidden-5120
+    #: shapes): 9..32 tokens 1.09-1.35x over e4m3 and 1.36-3.68x over the
+    #: library; 33..64 tokens level with e4m3, the library ahead at N > K
+    #: as for e4m3, so that tier's rule stands; 4 tokens 1.07-1.29x over
+    #: e4m3; 8 tokens level, and 0.91x of e4m3 at 20480x5120 (issue-bound).
+    #: The hidden >= 7168 exception is by analogy with e4m3, NOT MEASURED
+    #: for fp4, and neither is anything end to end.  Off by default;
+    #: ALPA_AMD_FP4=1 turns it on.
+    weight_fp4: bool = field(
+        default_factory=lambda: _env_bool("ALPA_AMD_FP4", False))
     #: split-KV decode attention (ops/csrc/attention_decode.hip) for
     #: single-token queries: ops.flash_attention at S_q == 1 outside
     #: autograd and ops.flash_attention_varlen.  "auto" (default) means

@@ -20,7 +20,11 @@ cached row), which global_config.kv_cache_fp8 turns on in the decoders.
 flash_attention_chunk and flash_attention_chunk_fp8 are the split-KV MFMA
 kernel for several query rows over a cache that already holds them (chunked
 prefill, draft verification, a multi-token turn), causal at the end of the
-cache.
+cache.  skinny_ok / skinny_linear are the packed decode GEMMs for up to 64
+tokens (dot2 GEMV up to 8, MFMA skinny GEMM for 9..64) over bf16, e4m3 or,
+under global_config.weight_fp4, MXFP4 weights: mxfp4_quantize and
+mxfp4_dequantize are that format (e2m1 codes, one e8m0 scale per 32 k),
+mxfp4_pack the layout its two kernels read.
 
 Kernel-level contract mirrors the reference's compiled-HLO op inventory
 (GEMM+epilogue, attention, LayerNorm, fused Adam,
@@ -51,6 +55,8 @@ __all__ = [
     "multi_tensor_sumsq",
     "hip_ops_available", "MoERouting", "moe_top2_route", "moe_dispatch",
     "moe_combine", "moe_fused_ok",
+    "skinny_ok", "skinny_linear", "mxfp4_quantize", "mxfp4_dequantize",
+    "mxfp4_pack",
 ]
 
 
@@ -1147,21 +1153,25 @@ def _skinny_mt(M: int) -> int:
     return MT
 
 
-def _skinny_legal_splits(K: int, MT: int) -> List[int]:
+def _skinny_legal_splits(K: int, MT: int, fp4: bool = False) -> List[int]:
     """Ascending split-K factors the kernel takes: s divides K/64 (keeps
     rounds = K/8/s a multiple of the 8-deep pipeline) and the LDS x-slice
-    (rounds * 16 * MT bytes) fits 64 KB."""
-    q = K // 64
+    (rounds * 16 * MT bytes) fits 64 KB.  The MXFP4 kernel
+    (csrc/skinny_fp4.hip) walks 32-k scale blocks in rounds of 8: K % 256 == 0,
+    s divides K/256, up to 8 tokens, the same LDS rule."""
+    if fp4 and (K <= 0 or K % 256 or MT > 8):
+        return []
+    q = K // (256 if fp4 else 64)
     return [s for s in range(1, q + 1)
             if q % s == 0 and (K // 8 // s) * 16 * MT <= 65536]
 
 
 @functools.lru_cache(maxsize=None)
-def _skinny_splits(N: int, K: int, M: int) -> Optional[int]:
+def _skinny_splits(N: int, K: int, M: int, fp4: bool = False) -> Optional[int]:
     """Split-K factor for the decode GEMV: a legal split
     (_skinny_legal_splits) whose grid (N/64 x s) should fill the 256 CUs.
     None = shapes unsupported."""
-    lds_ok = _skinny_legal_splits(K, _skinny_mt(M))
+    lds_ok = _skinny_legal_splits(K, _skinny_mt(M), fp4)
     if not lds_ok:
         return None
     # sweep-tuned (tools/skinny_bench.py): ~16 k-rounds per workgroup is
@@ -1223,17 +1233,67 @@ def _skinny_mfma_splits(N: int, K: int, M: int) -> Optional[int]:
     return legal[-1]
 
 
-def _skinny_cache(module, weight: torch.Tensor, fp8: bool):
-    """Packed [K/8, N, 8] weight (+ e4m3 scale), cached on the module and
-    keyed on the parameter version (in-place optimizer updates bump it)."""
-    key = (weight._version, fp8)
+#: the weight format of the packed decode kernels as the pack and tuning keys
+#: carry it: False = bf16, True = e4m3 with one scale, "mxfp4"
+_MXFP4 = "mxfp4"
+
+
+def _skinny_fmt(module):
+    """The format skinny_linear packs this module's weight in (see _MXFP4):
+    weight_fp4 before fp8_gemm, and neither for an _fp8_exclude module."""
+    from ..global_env import global_config
+    if getattr(module, "_fp8_exclude", False):
+        return False
+    if global_config.weight_fp4:
+        return _MXFP4
+    return bool(global_config.fp8_gemm)
+
+
+def mxfp4_quantize(w: torch.Tensor):
+    """w [N, K], K % 32 == 0 -> (codes uint8 [N, K/2], scales uint8
+    [N, K/32]) by the OCP MX rule: per block of 32 along K the e8m0 byte
+    E = clamp(floor(log2(amax)) - 2 + 127, 2, 252) (127 for a block of
+    zeros), every element x / 2^(E-127) rounded to the nearest e2m1 value,
+    ties to even, saturating at +-6, as sign<<3 | exp<<1 | mant with the even
+    k in the low nibble.  ValueError on a non-finite weight.  Plain torch on
+    the weight's device (reference.mxfp4_quantize): it runs once per weight."""
+    return ref.mxfp4_quantize(w)
+
+
+def mxfp4_dequantize(codes: torch.Tensor, scales: torch.Tensor,
+                     dtype=torch.bfloat16) -> torch.Tensor:
+    """The exact [N, K] weights that (codes, scales) of mxfp4_quantize stand
+    for; every value is a normal bf16.  Either device."""
+    return ref.mxfp4_dequantize(codes, scales, dtype)
+
+
+def mxfp4_pack(codes: torch.Tensor, scales: torch.Tensor):
+    """(codes [N, K/2], scales [N, K/32]), K % 256 == 0, in the one layout
+    both MXFP4 kernels read (csrc/skinny_fp4.h): wq [K/32, N, 16], a 16-byte
+    unit per row and scale block, and sq [K/256, N, 8], the 8 scale bytes of a
+    row's 256 k."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    assert K % 256 == 0 and scales.shape == (N, K // 32)
+    wq = codes.view(N, K // 32, 16).permute(1, 0, 2).contiguous()
+    sq = scales.view(N, K // 256, 8).permute(1, 0, 2).contiguous()
+    return wq, sq
+
+
+def _skinny_cache(module, weight: torch.Tensor, fmt):
+    """Packed weight and its scales, cached on the module and keyed on the
+    parameter version (in-place optimizer updates bump it) and the format
+    fmt (see _MXFP4): [K/8, N, 8] bf16 and None, e4m3 bytes and the fp32
+    scale, or mxfp4_pack's (wq, sq)."""
+    key = (weight._version, fmt)
     cached = getattr(module, "_skinny_pack", None)
     if cached is not None and cached[0] == key:
         return cached[1], cached[2]
     N, K = weight.shape
     with torch.no_grad():
         w = weight.contiguous()
-        if fp8:
+        if fmt == _MXFP4:
+            wp, scale = mxfp4_pack(*mxfp4_quantize(w))
+        elif fmt:
             amax = w.abs().amax().float().clamp_min(1e-12)
             scale = (amax / 448.0).reshape(1)
             q = (w.float() / scale).clamp(-448.0, 448.0).to(
@@ -1275,7 +1335,12 @@ def skinny_ok(x: torch.Tensor, weight: torch.Tensor, module=None) -> bool:
     M >= 16 issue-bound (SIMD-32 units: 2 cyc/VALU instr for wave64).
     9..64 tokens: the MFMA 16x16x32 kernel (csrc/skinny_mfma.hip) inside
     its envelope (N % 64 == 0, K % 256 == 0, a legal split); in "auto"
-    only where _skinny_mfma_auto says it was measured to win."""
+    only where _skinny_mfma_auto says it was measured to win.  Under
+    global_config.weight_fp4 the module's format is MXFP4 (_skinny_fmt) and
+    the gate is that of its two kernels (csrc/skinny_fp4.hip,
+    csrc/skinny_mfma_fp4.hip: K % 256 == 0 at every token count); "auto"
+    treats it as e4m3 (measured at hidden 5120, by analogy at hidden >= 7168:
+    global_config.weight_fp4)."""
     from ..global_env import global_config
     mode = global_config.skinny_gemm
     if mode in ("0", False) or torch.is_grad_enabled():
@@ -1294,42 +1359,52 @@ def skinny_ok(x: torch.Tensor, weight: torch.Tensor, module=None) -> bool:
         # (hipBLASLt already streams >= 5 TB/s there), but the
         # fp8-PACKED variant reads half the bytes and wins end-to-end
         # (OPT-66B fp8 decode 25.4 vs 28.99 ms/token measured)
-        fp8 = (global_config.fp8_gemm and
-               not getattr(module, "_fp8_exclude", False))
-        if not fp8:
+        if not _skinny_fmt(module):
             return False
     m = x.numel() // x.shape[-1]
     if m <= 8:
         return (N % 64 == 0 and K % 64 == 0
-                and _skinny_splits(N, K, m) is not None)
+                and _skinny_splits(N, K, m, _skinny_fmt(module) == _MXFP4)
+                is not None)
     # 9..64 tokens: the MFMA kernel, inside its envelope (and, in auto,
     # inside the measured win envelope: see global_config.skinny_gemm)
     if _skinny_mfma_splits(N, K, m) is None or x.data_ptr() % 16:
         return False
     if mode != "auto":
         return True
-    fp8 = bool(global_config.fp8_gemm and
-               not getattr(module, "_fp8_exclude", False))
-    return _skinny_mfma_auto(N, K, m, fp8)
+    return _skinny_mfma_auto(N, K, m, bool(_skinny_fmt(module)))
 
 
 _SKINNY_TUNED = {}
 
 
-def _skinny_tune(wp, x2, scale, N, K, MT, kernel="dot2"):
+def _skinny_gemm(kernel: str, fp4: bool):
+    """The binding of one kernel ("dot2" or "mfma") and weight format as
+    f(wp, x, scale, bias, N, K, splits); for MXFP4, wp and scale are
+    mxfp4_pack's wq and sq."""
+    ops = hip_ops()
+    if not fp4:
+        return ops.skinny_gemm_mfma if kernel == "mfma" else ops.skinny_gemm
+    gemm = ops.skinny_gemm_mfma_fp4 if kernel == "mfma" else ops.skinny_gemm_fp4
+    return lambda wq, x, sq, b, N, K, s: gemm(wq, sq, x, b, N, K, s)
+
+
+def _skinny_tune(wp, x2, scale, N, K, MT, kernel="dot2", fp4=False):
     """One-time per-(shape, MT, dtype, kernel) split autotune: the best
     split factor is shape- AND M-dependent (measured: rounds=16 wins 66B
     fp8 decode, the fill-first choice wins 13B batch-1), so time the legal
     candidates once and cache — the ~2 ms cost amortizes over the
     decode loop, like a library heuristic cache.  `kernel` is "dot2"
     (skinny_gemm, MT its padded tier) or "mfma" (skinny_gemm_mfma, MT its
-    token tier); the tag keeps their equal tiers apart in the cache."""
-    key = (N, K, MT, scale is not None, kernel)
+    token tier); the tag keeps their equal tiers apart in the cache.  The
+    key's format entry is False (bf16), True (e4m3) or "mxfp4" (fp4=True,
+    wp and scale being mxfp4_pack's wq and sq)."""
+    key = (N, K, MT, _MXFP4 if fp4 else scale is not None, kernel)
     got = _SKINNY_TUNED.get(key)
     if got is not None:
         return got
+    gemm = _skinny_gemm(kernel, fp4)
     if kernel == "mfma":
-        gemm = hip_ops().skinny_gemm_mfma
         legal = _skinny_mfma_legal_splits(K, MT)
         wgs = -(-N // 256)
         picks = (
@@ -1339,8 +1414,7 @@ def _skinny_tune(wp, x2, scale, N, K, MT, kernel="dot2"):
             next((c for c in legal if wgs * c >= 384), None),
             legal[-1])
     else:
-        gemm = hip_ops().skinny_gemm
-        legal = _skinny_legal_splits(K, MT)
+        legal = _skinny_legal_splits(K, MT, fp4)
         picks = (
             next((c for c in reversed(legal)
                   if K // 8 // c >= 16 and (N // 64) * c >= 1024), None),
@@ -1371,15 +1445,17 @@ def _skinny_tune(wp, x2, scale, N, K, MT, kernel="dot2"):
 def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
                   bias: Optional[torch.Tensor], module) -> torch.Tensor:
     """y = x @ W^T (+bias) through the packed decode kernels: the dot2
-    GEMV up to 8 tokens, the MFMA skinny GEMM for 9..64.  fp8 weights
-    (half the bytes/token) when global_config.fp8_gemm is on and the
-    module isn't _fp8_exclude; split-K fp32 partials are stored and
+    GEMV up to 8 tokens, the MFMA skinny GEMM for 9..64.  The weights are
+    packed once per module (_skinny_cache) as bf16, as e4m3 with one scale
+    (half the bytes/token) under global_config.fp8_gemm, or as MXFP4 (e2m1
+    nibbles and e8m0 block scales, 4.25 bits a weight, dequantized exactly
+    in registers) under global_config.weight_fp4, which goes first; a module
+    marked _fp8_exclude stays bf16.  Split-K fp32 partials are stored and
     reduced in a fixed order by a finalize launch (deterministic, no
-    atomics).  Inference only."""
-    from ..global_env import global_config
-    fp8 = (global_config.fp8_gemm and
-           not getattr(module, "_fp8_exclude", False))
-    wp, scale = _skinny_cache(module, weight, fp8)
+    atomics).  Inference only; on the CPU see reference.skinny_linear_fp4."""
+    fmt = _skinny_fmt(module)
+    fp4 = fmt == _MXFP4
+    wp, scale = _skinny_cache(module, weight, fmt)
     N, K = weight.shape
     shape = x.shape
     x2 = x.reshape(-1, K).contiguous()
@@ -1388,15 +1464,15 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
     # up to 8 tokens: the dot2 kernel; 9..64 (skinny_ok has checked the
     # envelope): the MFMA kernel, over the same packed weights
     if M <= 8:
-        kernel, gemm = "dot2", hip_ops().skinny_gemm
-        MT, rule = _skinny_mt(M), _skinny_splits
+        kernel, MT = "dot2", _skinny_mt(M)
+        rule = functools.partial(_skinny_splits, fp4=fp4)
     else:
-        kernel, gemm = "mfma", hip_ops().skinny_gemm_mfma
-        MT, rule = _skinny_mfma_mt(M), _skinny_mfma_splits
+        kernel, MT, rule = "mfma", _skinny_mfma_mt(M), _skinny_mfma_splits
     if torch.cuda.is_current_stream_capturing():
-        splits = _SKINNY_TUNED.get((N, K, MT, scale is not None, kernel)) \
+        splits = _SKINNY_TUNED.get(
+            (N, K, MT, _MXFP4 if fp4 else scale is not None, kernel)) \
             or rule(N, K, M)
     else:
-        splits = _skinny_tune(wp, x2, scale, N, K, MT, kernel)
-    y = gemm(wp, x2, scale, b, N, K, splits)
+        splits = _skinny_tune(wp, x2, scale, N, K, MT, kernel, fp4)
+    y = _skinny_gemm(kernel, fp4)(wp, x2, scale, b, N, K, splits)
     return y.reshape(*shape[:-1], N)

@@ -415,6 +415,92 @@ at::Tensor skinny_gemm_mfma(const at::Tensor& wp, const at::Tensor& x,
   return y;
 }
 
+// The packed MXFP4 weights of both fp4 entries (skinny_fp4.h): wq
+// [K/32, N, 16] nibble bytes, sq [K/256, N, 8] e8m0 scale bytes.
+void check_fp4_weights(const at::Tensor& wq, const at::Tensor& sq, int64_t N,
+                       int64_t K) {
+  TORCH_CHECK(N > 0 && N % 64 == 0, "N must be a positive multiple of 64");
+  TORCH_CHECK(K > 0 && K % 256 == 0,
+              "K must be a positive multiple of 256 (whole 32-k scale blocks "
+              "in whole 8-block rounds), got ", K);
+  check_vec(wq, "wq", at::kByte, N * K / 2, wq);
+  TORCH_CHECK(wq.dim() == 3 && wq.size(1) == N && wq.size(2) == 16,
+              "wq must be [K/32, N, 16], got ", wq.sizes());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(wq.const_data_ptr()) % 16 == 0,
+              "wq must be 16-byte aligned");
+  check_vec(sq, "sq", at::kByte, N * K / 32, wq);
+  TORCH_CHECK(sq.dim() == 3 && sq.size(1) == N && sq.size(2) == 8,
+              "sq must be [K/256, N, 8], got ", sq.sizes());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(sq.const_data_ptr()) % 8 == 0,
+              "sq must be 8-byte aligned");
+}
+
+// y[M,N] bf16 = x[M,K] @ W^T (+ bias) for M <= 8 over MXFP4 weights
+// (skinny_fp4.hip): split-K partials, then the deterministic finalize.
+at::Tensor skinny_gemm_fp4(const at::Tensor& wq, const at::Tensor& sq,
+                           const at::Tensor& x,
+                           const c10::optional<at::Tensor>& bias, int64_t N,
+                           int64_t K, int64_t splits) {
+  check_fp4_weights(wq, sq, N, K);
+  if (bias.has_value()) check_vec(*bias, "bias", at::kBFloat16, N, wq);
+  auto [M, Kx] = check_rows(x, "x", 256, wq);
+  TORCH_CHECK(x.dim() == 2 && Kx == K, "x must be [M, K]");
+  TORCH_CHECK(M >= 1 && M <= 8, "x must have 1 to 8 rows, got ", M);
+  const int64_t MT = M <= 4 ? 4 : 8;
+  TORCH_CHECK(splits >= 1 && (K / 256) % splits == 0 &&
+                  (K / splits) * 2 * MT <= SKINNY_FP4_LDS_MAX,
+              "splits must divide K/256 and leave (K/splits)*2*MT <= ",
+              SKINNY_FP4_LDS_MAX, " bytes of LDS, got ", splits);
+  at::Tensor xp = x;
+  if (MT != M) {
+    xp = at::zeros({MT, K}, x.options());
+    xp.narrow(0, 0, M).copy_(x);
+  }
+  auto part = at::empty({splits, MT, N}, x.options().dtype(at::kFloat));
+  auto y = at::empty({M, N}, x.options());
+  HIP_OK(launch_skinny_fp4(
+      wq.const_data_ptr(), sq.const_data_ptr(), xp.const_data_ptr(),
+      (float*)part.mutable_data_ptr(),
+      bias.has_value() ? bias->const_data_ptr() : nullptr,
+      y.mutable_data_ptr(), M, MT, N, K, (int)splits, cur_stream()));
+  return y;
+}
+
+// The same product for 9 <= M <= 64 through the MXFP4 MFMA kernel
+// (skinny_mfma_fp4.hip), over the same packed weights; launches and x as
+// skinny_gemm_mfma.
+at::Tensor skinny_gemm_mfma_fp4(const at::Tensor& wq, const at::Tensor& sq,
+                                const at::Tensor& x,
+                                const c10::optional<at::Tensor>& bias,
+                                int64_t N, int64_t K, int64_t splits) {
+  check_fp4_weights(wq, sq, N, K);
+  if (bias.has_value()) {
+    check_vec(*bias, "bias", at::kBFloat16, N, wq);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(bias->const_data_ptr()) % 8 == 0,
+                "bias must be 8-byte aligned");
+  }
+  auto [M, Kx] = check_rows(x, "x", 256, wq);
+  TORCH_CHECK(x.dim() == 2 && Kx == K, "x must be [M, K]");
+  TORCH_CHECK(M >= 9 && M <= 64, "x must have 9 to 64 rows, got ", M);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.const_data_ptr()) % 16 == 0,
+              "x must be 16-byte aligned");
+  const int64_t MT = M <= 16 ? 16 : M <= 32 ? 32 : 64;
+  TORCH_CHECK(splits >= 1 && (K / 256) % splits == 0 &&
+                  MT * (K / splits + 16) * 2 <= SKINNY_MFMA_LDS_MAX,
+              "splits must divide K/256 and leave MT*(K/splits+16)*2 <= ",
+              SKINNY_MFMA_LDS_MAX, " bytes of LDS, got ", splits);
+  at::Tensor part;
+  if (splits > 1)
+    part = at::empty({splits, M, N}, x.options().dtype(at::kFloat));
+  auto y = at::empty({M, N}, x.options());
+  HIP_OK(launch_skinny_mfma_fp4(
+      wq.const_data_ptr(), sq.const_data_ptr(), x.const_data_ptr(),
+      splits > 1 ? (float*)part.mutable_data_ptr() : nullptr,
+      bias.has_value() ? bias->const_data_ptr() : nullptr,
+      y.mutable_data_ptr(), M, N, K, (int)splits, cur_stream()));
+  return y;
+}
+
 // -------------------------------- AdamW ----------------------------------
 
 void adamw_step_raw(const at::Tensor& descs, const at::Tensor& chunks,
@@ -1296,6 +1382,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "decode GEMV over packed weights (gfx950)");
   m.def("skinny_gemm_mfma", &skinny_gemm_mfma,
         "MFMA decode GEMM for 9..64 tokens over packed weights (gfx950)");
+  m.def("skinny_gemm_fp4", &skinny_gemm_fp4,
+        "decode GEMV for up to 8 tokens over packed MXFP4 weights (gfx950)");
+  m.def("skinny_gemm_mfma_fp4", &skinny_gemm_mfma_fp4,
+        "MFMA decode GEMM for 9..64 tokens over packed MXFP4 weights "
+        "(gfx950)");
   m.def("adamw_step_raw", &adamw_step_raw, "multi-tensor AdamW (gfx950)",
         py::arg("descs"), py::arg("chunks"), py::arg("step"), py::arg("lr"),
         py::arg("beta1"), py::arg("beta2"), py::arg("eps"),

@@ -102,6 +102,28 @@ hipError_t launch_skinny_mfma(const void* wp, const void* x,
                               int64_t M, int64_t N, int64_t K, int splits,
                               hipStream_t stream);
 
+// ---- skinny_fp4.hip ----
+// MXFP4 weights packed as skinny_fp4.h describes: wq [K/32, N, 16] nibble
+// blocks, sq [K/256, N, 8] e8m0 scale bytes, both 16- / 8-byte aligned.
+// 1 <= M <= MT, MT = 4 or 8, x [MT, K] with zero rows past M, N % 64 == 0,
+// K % 256 == 0, splits divides K/256 and the staged x slice
+// (K/splits) * 2 * MT bytes is at most SKINNY_FP4_LDS_MAX.  part: fp32
+// [splits, MT, N].
+#define SKINNY_FP4_LDS_MAX (64 * 1024)
+hipError_t launch_skinny_fp4(const void* wq, const void* sq, const void* x,
+                             float* part, const void* bias_or_null, void* y,
+                             int64_t M, int64_t MT, int64_t N, int64_t K,
+                             int splits, hipStream_t stream);
+
+// ---- skinny_mfma_fp4.hip ----
+// the envelope, part_or_null and x of launch_skinny_mfma, over the packed
+// MXFP4 weights of launch_skinny_fp4
+hipError_t launch_skinny_mfma_fp4(const void* wq, const void* sq,
+                                  const void* x, float* part_or_null,
+                                  const void* bias_or_null, void* y,
+                                  int64_t M, int64_t N, int64_t K, int splits,
+                                  hipStream_t stream);
+
 // ---- cross_entropy.hip ----
 hipError_t launch_ce_fwd(const void* logits, const int64_t* targets,
                          float* loss, float* lse, int64_t N, int64_t V,

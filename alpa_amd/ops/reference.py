@@ -589,3 +589,70 @@ def moe_combine_bwd(dout: torch.Tensor, y: torch.Tensor, w1: torch.Tensor,
     dw1 = (df * _moe_rows(yf, slot1)).sum(-1).to(w1.dtype)
     dw2 = (df * _moe_rows(yf, slot2)).sum(-1).to(w2.dtype)
     return dy, dw1, dw2
+
+
+# ------------------- MXFP4 weights (OCP microscaling) ------------------------
+# e2m1 codes sign<<3 | exp<<1 | mant and one e8m0 scale byte per 32 k.  These
+# functions are the format's specification; ops.mxfp4_quantize and
+# ops.mxfp4_dequantize are these, and skinny_linear_fp4 is the oracle of the
+# two MXFP4 kernels.
+#: the 8 magnitudes of e2m1, by code & 7
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mxfp4_quantize(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """w [N, K], K % 32 == 0 -> (codes uint8 [N, K/2], scales uint8
+    [N, K/32]).  Per block of 32 along K: E = clamp(floor(log2(amax)) - 2 +
+    127, 2, 252), which keeps every dequantized value a normal bf16 (127 for
+    a block of zeros); each element x / 2^(E-127), an exact fp32 product, is
+    rounded to the nearest e2m1 value, ties to the even code, saturating at
+    +-6.  The even k goes in the low nibble.  Only integer and exact fp32
+    steps, so every device gives the same bytes.  ValueError on a non-finite
+    weight."""
+    N, K = w.shape
+    if K % 32:
+        raise ValueError(f"mxfp4_quantize: K must be a multiple of 32, got {K}")
+    xf = w.detach().float().reshape(N, K // 32, 32)
+    if not bool(torch.isfinite(xf).all()):
+        raise ValueError("mxfp4_quantize: the weight holds a NaN or an Inf")
+    amax = xf.abs().amax(dim=-1)
+    # floor(log2(amax)) + 127 is the fp32 exponent field (0 for subnormals,
+    # which the clamp covers)
+    field = (amax.view(torch.int32) >> 23) & 0xFF
+    E = torch.where(amax == 0, torch.full_like(field, 127),
+                    (field - 2).clamp(2, 252))
+    inv = ((254 - E) << 23).view(torch.float32)  # 2^(127-E)
+    a = (xf * inv.unsqueeze(-1)).abs()
+    # one step per midpoint; >= where the tie goes up to the even code
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25)
+            + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    code = (code | (torch.signbit(xf).to(torch.uint8) << 3)).reshape(N, K)
+    codes = code[:, 0::2] | (code[:, 1::2] << 4)
+    return codes.contiguous(), E.to(torch.uint8)
+
+
+def mxfp4_dequantize(codes: torch.Tensor, scales: torch.Tensor,
+                     dtype=torch.bfloat16) -> torch.Tensor:
+    """The [N, K] weights that (codes, scales) stand for: e2m1 value times
+    2^(E-127), exact in fp32 and, for 2 <= E <= 252, in bf16."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    nib = torch.stack((codes & 0xF, codes >> 4), dim=-1).reshape(N, K).long()
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES),
+                       dtype=torch.float32, device=codes.device)
+    E = scales.to(torch.int32)
+    # 2^(E-127) from the exponent field; E = 0 is the fp32 subnormal 2^-127
+    factor = torch.where(E == 0, torch.full_like(E, 0x00400000),
+                         E << 23).view(torch.float32)
+    val = lut[nib].reshape(N, K // 32, 32) * factor.unsqueeze(-1)
+    return val.reshape(N, K).to(dtype)
+
+
+def skinny_linear_fp4(x: torch.Tensor, codes: torch.Tensor,
+                      scales: torch.Tensor, bias=None) -> torch.Tensor:
+    """y = x @ dequantize(codes, scales)^T (+ bias): fp32 matmul on the exact
+    weights, rounded once to x's dtype."""
+    w = mxfp4_dequantize(codes, scales, torch.float32)
+    y = x.float().reshape(-1, w.shape[1]) @ w.t()
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(x.dtype).reshape(*x.shape[:-1], w.shape[0])

@@ -1,7 +1,10 @@
 """Numerics + bandwidth of the skinny decode kernels vs torch.matmul at
 decode shapes: the dot2 GEMV (csrc/skinny_gemm.hip) and, for 9..64 tokens
 inside its envelope, the MFMA skinny GEMM (csrc/skinny_mfma.hip) as a third
-column.  Every column is the time of one whole call (all its launches).
+column.  After the bf16 and e4m3 rows come the MXFP4 rows (fp4:
+csrc/skinny_fp4.hip up to 8 tokens, csrc/skinny_mfma_fp4.hip for 9..64,
+against the same library bf16 GEMM; rel is against the dequantized weights).
+Every column is the time of one whole call (all its launches).
 SKINNY_SWEEP=1 sweeps the legal splits of both kernels, SKINNY_REPEAT=n
 prints the whole table n times (the spread between the copies is the
 run-to-run noise); HBM bandwidth is the bound of these GEMMs, so the floor
@@ -13,8 +16,10 @@ import time
 import torch
 
 sys.path.insert(0, ".")
-from alpa_amd.ops import (_skinny_mfma_legal_splits, _skinny_mfma_mt,
-                          _skinny_mfma_splits, _skinny_splits)
+from alpa_amd.ops import (_skinny_legal_splits, _skinny_mfma_legal_splits,
+                          _skinny_mfma_mt, _skinny_mfma_splits, _skinny_mt,
+                          _skinny_splits, mxfp4_dequantize, mxfp4_pack,
+                          mxfp4_quantize)
 from alpa_amd.ops._backend import hip_ops
 
 PEAK_TBS = float(os.environ.get("SKINNY_PEAK_TBS", "8.0"))
@@ -91,6 +96,45 @@ def run(M, N, K, fp8):
     print(line, flush=True)
 
 
+def run_fp4(M, N, K):
+    """One MXFP4 row: the kernel that serves M tokens, at the rule's split
+    (and, under SKINNY_SWEEP=1, at the best legal one)."""
+    x = (torch.randn(M, K, device="cuda") * 0.5).to(torch.bfloat16)
+    w = (torch.randn(N, K, device="cuda") * 0.05).to(torch.bfloat16)
+    codes, scales = mxfp4_quantize(w)
+    wq, sq = mxfp4_pack(codes, scales)
+    ref = x.float() @ mxfp4_dequantize(codes, scales).float().t()
+    if M <= 8:
+        name, gemm = "dot2", hip_ops().skinny_gemm_fp4
+        s = _skinny_splits(N, K, M, True)
+        legal = _skinny_legal_splits(K, _skinny_mt(M), True)
+    else:
+        name, gemm = "mfma", hip_ops().skinny_gemm_mfma_fp4
+        s = _skinny_mfma_splits(N, K, M)
+        legal = _skinny_mfma_legal_splits(K, _skinny_mfma_mt(M))
+    if s is None:
+        return
+
+    def fp4(c):
+        return gemm(wq, sq, x, None, N, K, c)
+    rel = (fp4(s) - ref).abs().mean() / ref.abs().mean().clamp_min(1e-9)
+    rule, t_k = s, bench(lambda: fp4(s))
+    t_rule = t_k
+    if os.environ.get("SKINNY_SWEEP") == "1":
+        for s2 in legal:
+            t2 = bench(lambda: fp4(s2), 100)
+            if t2 < t_k:
+                t_k, s = t2, s2
+    t_t = bench(lambda: x @ w.t())
+    bytes_w = N * K // 2 + N * K // 32
+    floor = bytes_w / PEAK_TBS / 1e6
+    print(f"M={M:3d} N={N:6d} K={K:6d} fp4  {name} splits={s:2d} (rule "
+          f"{rule:2d}: {t_rule:6.1f} us) rel={rel.item():.4f} {t_k:7.1f} us "
+          f"({bytes_w / t_k / 1e6:5.2f} TB/s, {floor / t_k:4.0%} of the HBM "
+          f"floor)  torch {t_t:7.1f} us  vs torch {t_t / t_k:4.2f}x",
+          flush=True)
+
+
 _shapes = os.environ.get("SKINNY_SHAPES")
 SHAPES = ([tuple(map(int, t.split("x"))) for t in _shapes.split(",")]
           if _shapes else [(5120, 5120), (15360, 5120), (20480, 5120),
@@ -102,3 +146,6 @@ for rep in range(int(os.environ.get("SKINNY_REPEAT", "1"))):
         for (N, K) in SHAPES:
             for M in MS:
                 run(M, N, K, fp8)
+    for (N, K) in SHAPES:
+        for M in MS:
+            run_fp4(M, N, K)
