@@ -161,6 +161,7 @@ class TrainState:
                                             betas=betas,
                                             weight_decay=weight_decay,
                                             **clip)
+            state._attach_weight_twins()
         return state
 
     @classmethod
@@ -218,7 +219,24 @@ class TrainState:
                                 weight_decay=weight_decay,
                                 max_grad_norm=max_grad_norm,
                                 grad_norm_groups=expert_groups or None)
+        state._attach_weight_twins()
         return state
+
+    def _attach_weight_twins(self):
+        """Serial/dp/tp states with whole parameters (zero_stage 0): the
+        optimizer keeps a transposed copy of each linear weight for its dX
+        GEMM (AdamW.attach_weight_twins, which also decides when not to).
+        ZeRO-2 updates flat shards and ZeRO-3 gathered ones, so neither can
+        write a twin in its step, and they keep dX on the weight itself.
+        Models on the GPU only: the layout is a hipBLASLt matter, and a
+        CPU model keeps the summation order of its GEMMs (the optimizer
+        still takes an explicit attach_weight_twins there, through the
+        reference path)."""
+        # optimizer_cls may be a user class without the method
+        attach = getattr(self.optimizer, "attach_weight_twins", None)
+        first = next(iter(self.model.parameters()), None)
+        if attach is not None and first is not None and first.is_cuda:
+            attach(self.model)
 
     def _install_zero3(self, lr, betas, weight_decay, max_grad_norm=None):
         """ZeRO-3: block params sharded + JIT-gathered (parallel/zero3.py);

@@ -130,6 +130,20 @@ class GlobalConfig:
     kv_cache_fp8: bool = field(
         default_factory=lambda: _env_bool("ALPA_AMD_KV_FP8", False))
 
+    #: bf16 dX GEMMs of the parallel linear layers read a transposed copy
+    #: of the weight (its "twin", ops.weight_twin) that the fused AdamW
+    #: kernel writes next to the weight: dY @ W (NN) becomes the TN GEMM
+    #: the forward runs, which hipBLASLt serves 20-30 % faster
+    #: (docs/BENCHMARK.md, "dX on weight twins").  Costs 2 B per linear-
+    #: weight parameter.  Twins exist only where TrainState attaches them
+    #: (serial/dp/tp bf16 training on the GPU; not ZeRO-2/3, the pipeline
+    #: stages, fp8_gemm, or a model whose twins would take more than 1/32
+    #: of the GPU's memory: AdamW.attach_weight_twins).  Off when the TrainState is
+    #: created: nothing is allocated.  Turned off later: the optimizer
+    #: keeps the twins current but dX reads W, so tests can run both
+    #: routes in one process.  ALPA_AMD_WEIGHT_TWIN=0 turns it off
+    weight_twin: bool = field(
+        default_factory=lambda: _env_bool("ALPA_AMD_WEIGHT_TWIN", True))
     #: compute dX with the bf16 MASTER weight instead of the fp8 wqt
     #: cache: halves the fp8 weight-cache footprint (the +30 GB dual
     #: cache at 15B pushes hipGraph capture OOM -> eager, see

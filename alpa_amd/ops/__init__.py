@@ -24,7 +24,9 @@ cache.  skinny_ok / skinny_linear are the packed decode GEMMs for up to 64
 tokens (dot2 GEMV up to 8, MFMA skinny GEMM for 9..64) over bf16, e4m3 or,
 under global_config.weight_fp4, MXFP4 weights: mxfp4_quantize and
 mxfp4_dequantize are that format (e2m1 codes, one e8m0 scale per 32 k),
-mxfp4_pack the layout its two kernels read.
+mxfp4_pack the layout its two kernels read.  weight_twin and its helpers
+keep the transposed copies of linear weights that fused_adamw writes and
+linear_bias's dX GEMM reads.
 
 Kernel-level contract mirrors the reference's compiled-HLO op inventory
 (GEMM+epilogue, attention, LayerNorm, fused Adam,
@@ -34,6 +36,7 @@ from __future__ import annotations
 
 import functools
 import math
+import weakref
 from typing import List, NamedTuple, Optional
 
 import torch
@@ -52,7 +55,9 @@ __all__ = [
     "softmax_cross_entropy",
     "softmax_cross_entropy_partial", "softmax_cross_entropy_combine",
     "softmax_cross_entropy_shard_bwd", "vocab_ce_fused_ok", "fused_adamw",
-    "multi_tensor_sumsq",
+    "multi_tensor_sumsq", "weight_twin", "weight_twin_eligible",
+    "register_weight_twin", "weight_twin_written", "valid_weight_twin",
+    "invalidate_weight_twin",
     "hip_ops_available", "MoERouting", "moe_top2_route", "moe_dispatch",
     "moe_combine", "moe_fused_ok",
     "skinny_ok", "skinny_linear", "mxfp4_quantize", "mxfp4_dequantize",
@@ -237,26 +242,36 @@ def bias_add(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
 
 
 class _LinearBias(torch.autograd.Function):
-    """y = x @ w.T + bias via torch.addmm: hipBLASLt fuses the bias
-    epilogue into the GEMM (measured free — matmul+separate add cost
-    ~16 ms per GPT-2.6B step, tools/addmm_probe.py).  Backward runs the
-    standard dX/dW GEMMs and the HIP column-sum for db."""
+    """y = x @ w.T (+ bias).  With a bias, via torch.addmm: hipBLASLt fuses
+    the bias epilogue into the GEMM (measured free — matmul+separate add
+    cost ~16 ms per GPT-2.6B step, tools/addmm_probe.py).  Backward runs
+    the standard dX/dW GEMMs and the HIP column-sum for db; dX reads the
+    weight's twin (valid_weight_twin) where it has one, which turns the NN
+    GEMM dY @ w into the TN form dY @ twin.t() of the same product."""
 
     @staticmethod
     def forward(ctx, x, w, bias):
         shape = x.shape
         x2 = x.reshape(-1, shape[-1])
-        y = torch.addmm(bias, x2, w.t())
+        if bias is None:
+            y = torch.matmul(x2, w.t())
+        else:
+            y = torch.addmm(bias, x2, w.t())
+            ctx.bias_dtype = bias.dtype
         ctx.save_for_backward(x2, w)
-        ctx.bias_dtype = bias.dtype
+        ctx.has_bias = bias is not None
         return y.reshape(*shape[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, g):
         x2, w = ctx.saved_tensors
         g2 = g.reshape(-1, g.shape[-1]).contiguous()
-        dx = (g2 @ w).reshape(*g.shape[:-1], w.shape[1])
+        twin = valid_weight_twin(w)
+        dx = (g2 @ w) if twin is None else (g2 @ twin.t())
+        dx = dx.reshape(*g.shape[:-1], w.shape[1])
         dw = g2.t() @ x2
+        if not ctx.has_bias:
+            return dx, dw, None
         if use_hip(g2) and g2.dtype == torch.bfloat16:
             db = _colsum(g2, ctx.bias_dtype)
         else:
@@ -265,9 +280,9 @@ class _LinearBias(torch.autograd.Function):
 
 
 def linear_bias(x: torch.Tensor, w: torch.Tensor,
-                bias: torch.Tensor) -> torch.Tensor:
-    """F.linear with the bias fused into the hipBLASLt epilogue and the
-    bias grad on the HIP column-sum."""
+                bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """F.linear with the bias (if any) fused into the hipBLASLt epilogue,
+    the bias grad on the HIP column-sum and dX on the weight's twin."""
     return _LinearBias.apply(x, w, bias)
 
 
@@ -871,16 +886,21 @@ def softmax_cross_entropy_shard_bwd(dloss: torch.Tensor,
 
 
 _ADAM_CHUNK = 16384  # must match ADAM_CHUNK in csrc/adamw.hip
+_ADAM_TILE = 64  # must match ADAM_TILE in csrc/adamw.hip
 _ADAM_TABLE_CACHE: dict = {}
 
 
 def _upload_tables(rows, dev):
-    """rows: (p, g, m, v, numel, is_bf16) per tensor, pointers as ints.
-    Returns the device-side descriptor table and the chunk table that maps
-    each workgroup to (tensor_idx, chunk_idx)."""
+    """rows: (p, g, m, v, numel, is_bf16, twin, rows | cols << 32) per
+    tensor, pointers as ints; twin is 0 for a tensor without one.  Returns
+    the device-side descriptor table and the chunk table that maps each
+    workgroup to (tensor_idx, chunk_idx): one per started _ADAM_CHUNK
+    elements, or one per _ADAM_TILE x _ADAM_TILE tile of a tensor with a
+    twin (whose rows and cols are multiples of the tile)."""
     n = len(rows)
-    descs = torch.tensor(rows, dtype=torch.int64).reshape(n, 6)
-    counts = [(r[4] + _ADAM_CHUNK - 1) // _ADAM_CHUNK for r in rows]
+    descs = torch.tensor(rows, dtype=torch.int64).reshape(n, 8)
+    counts = [r[4] // (_ADAM_TILE * _ADAM_TILE) if r[6] else
+              (r[4] + _ADAM_CHUNK - 1) // _ADAM_CHUNK for r in rows]
     tensor_idx = torch.repeat_interleave(
         torch.arange(n, dtype=torch.int32),
         torch.tensor(counts, dtype=torch.int64))
@@ -890,27 +910,38 @@ def _upload_tables(rows, dev):
     return descs.to(dev), chunks.to(dev)
 
 
-def _adam_tables(params, grads, exp_avgs, exp_avg_sqs):
+def _adam_tables(params, grads, exp_avgs, exp_avg_sqs, twins=None):
     """Build (and cache) the device-side tensor-descriptor + chunk tables
     consumed by the multi-tensor AdamW kernel (one launch per step)."""
+    if twins is None:
+        twins = [None] * len(params)
     # the key covers every field a descriptor row holds: a second optimizer
     # over the same params brings new moment buffers, and the caching
     # allocator can hand the same base pointers to tensors of another
     # size or dtype
     key = tuple((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
-                 p.numel(), p.dtype)
-                for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs))
+                 p.numel(), p.dtype, 0 if t is None else t.data_ptr())
+                for p, g, m, v, t in zip(params, grads, exp_avgs,
+                                         exp_avg_sqs, twins))
     hit = _ADAM_TABLE_CACHE.get(key)
     if hit is not None:
         return hit
     rows = []
-    for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
+    for p, g, m, v, t in zip(params, grads, exp_avgs, exp_avg_sqs, twins):
         assert p.is_contiguous() and g.is_contiguous()
         assert m.dtype == torch.float32 and v.dtype == torch.float32
         assert p.dtype == g.dtype and p.dtype in (torch.bfloat16,
                                                   torch.float32)
+        twin_ptr = shape = 0
+        if t is not None:
+            assert g.shape == p.shape
+            if p.is_cuda:
+                hip_ops().adamw_check_twin(p, m, v, t)
+            twin_ptr = t.data_ptr()
+            shape = p.shape[0] | (p.shape[1] << 32)
         rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
-                     p.numel(), 1 if p.dtype == torch.bfloat16 else 0))
+                     p.numel(), 1 if p.dtype == torch.bfloat16 else 0,
+                     twin_ptr, shape))
     tbl = _upload_tables(rows, params[0].device)
     _ADAM_TABLE_CACHE[key] = tbl
     return tbl
@@ -933,7 +964,7 @@ def _sumsq_tables(tensors):
         assert t.is_contiguous()
         assert t.dtype in (torch.bfloat16, torch.float32)
         rows.append((0, t.data_ptr(), 0, 0, t.numel(),
-                     1 if t.dtype == torch.bfloat16 else 0))
+                     1 if t.dtype == torch.bfloat16 else 0, 0, 0))
     dev = tensors[0].device
     descs, chunks = _upload_tables(rows, dev)
     partials = torch.empty(chunks.shape[0], dtype=torch.float32, device=dev)
@@ -972,9 +1003,16 @@ def fused_adamw(params: List[torch.Tensor], grads: List[torch.Tensor],
                 eps: float = 1e-8, weight_decay: float = 0.0,
                 grad_scale: float = 1.0,
                 grad_sumsq: Optional[torch.Tensor] = None,
-                max_grad_norm: Optional[float] = None) -> None:
+                max_grad_norm: Optional[float] = None,
+                twins: Optional[List[Optional[torch.Tensor]]] = None) -> None:
     """Multi-tensor AdamW update, in place — ONE kernel launch for all
     params.
+
+    ``twins``, aligned with ``params``, gives for each parameter either
+    None or a bf16 [cols, rows] tensor that receives the transpose of the
+    updated [rows, cols] parameter in the same launch (see
+    :func:`weight_twin_eligible` for which parameters can have one).  A
+    step that changes nothing (non-finite norm, below) leaves it alone too.
 
     Params may be bf16 (fp32 master math happens inside the kernel against
     the fp32 exp_avg/exp_avg_sq state).  Analog of the fused Adam the
@@ -998,15 +1036,128 @@ def fused_adamw(params: List[torch.Tensor], grads: List[torch.Tensor],
         raise ValueError(f"max_grad_norm must be > 0, got {max_grad_norm}")
     if not params:
         return
+    if twins is not None and len(twins) != len(params):
+        raise ValueError("twins must be aligned with params")
     if use_hip(params[0]):
-        descs, chunks = _adam_tables(params, grads, exp_avgs, exp_avg_sqs)
+        descs, chunks = _adam_tables(params, grads, exp_avgs, exp_avg_sqs,
+                                     twins)
         hip_ops().adamw_step_raw(descs, chunks, step, lr, beta1, beta2, eps,
                                  weight_decay, grad_scale, grad_sumsq,
                                  max_grad_norm or 0.0)
     else:
         ref.adamw_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1,
                        beta2, eps, weight_decay, grad_scale, grad_sumsq,
-                       max_grad_norm)
+                       max_grad_norm, twins)
+
+
+# ------------------------------ weight twins ------------------------------
+# A twin is a contiguous bf16 copy of W.t() for a linear weight W [out, in]:
+# with it the dX GEMM dY @ W becomes dY @ twin.t(), the K-contiguous (TN)
+# layout of the forward, which hipBLASLt runs 20-30 % faster than the NN
+# layout (docs/BENCHMARK.md, "dX on weight twins").  It is derived state:
+# it lives here, keyed weakly by the parameter, never in the module, and is
+# kept current by the optimizer that registered it (fused_adamw writes it).
+
+class _TwinEntry:
+    """twin, and the state of the weight it was built from: its version
+    counter and the address of its storage."""
+    __slots__ = ("twin", "version", "ptr")
+
+    def __init__(self, twin, w):
+        self.twin = twin
+        self.mark_current(w)
+
+    def mark_current(self, w):
+        self.version, self.ptr = w._version, w.data_ptr()
+
+    def is_current(self, w):
+        return self.version == w._version and self.ptr == w.data_ptr()
+
+
+# id(parameter) -> entry, dropped when the parameter dies (a tensor cannot
+# key a WeakKeyDictionary: its == is elementwise)
+_WEIGHT_TWINS: dict = {}
+
+
+def weight_twin_eligible(w: torch.Tensor) -> bool:
+    """Can `w` have a twin: 2-D and contiguous, and on the GPU what the
+    tiled path of the AdamW kernel asks for: bf16, 16-byte aligned, rows
+    and cols multiples of its tile.  (The CPU reference takes any dtype and
+    shape, so CPU runs go through the same plumbing.)"""
+    if w.dim() != 2 or not w.is_contiguous() or not w.is_floating_point():
+        return False
+    if not w.is_cuda:
+        return True
+    return (w.dtype == torch.bfloat16 and w.data_ptr() % 16 == 0
+            and w.shape[0] % _ADAM_TILE == 0 and w.shape[1] % _ADAM_TILE == 0)
+
+
+@torch.no_grad()
+def register_weight_twin(w: torch.Tensor) -> Optional[torch.Tensor]:
+    """Allocate, fill and register the twin of `w`; None (and nothing
+    allocated) if `w` is not eligible.  The caller takes on keeping it
+    current: see :func:`weight_twin_written`."""
+    if not weight_twin_eligible(w):
+        return None
+    entry = _WEIGHT_TWINS.get(id(w))
+    if entry is None:
+        entry = _TwinEntry(w.t().contiguous(), w)
+        _WEIGHT_TWINS[id(w)] = entry
+        weakref.finalize(w, _WEIGHT_TWINS.pop, id(w), None)
+    return entry.twin
+
+
+@torch.no_grad()
+def weight_twin(w: torch.Tensor) -> Optional[torch.Tensor]:
+    """The registered twin of `w`, current, or None if it has none.
+    fused_adamw does not bump `w._version`; in-place writers that autograd
+    sees (load_state_dict, a checkpoint restore, init, copy_) do, and a
+    swap of the storage (`w.data = ...`, `model.to(...)`) moves
+    `w.data_ptr()`; after either the twin is rebuilt here before it is
+    handed out.  NOT caught: an in-place write through `w.data`
+    (`w.data.copy_(...)`) and a second optimizer stepping `w` without
+    twins; after those, call :func:`invalidate_weight_twin`.  During
+    stream capture a rebuild would be baked into the graph and replayed
+    every step, so a stale twin is an error there."""
+    entry = _WEIGHT_TWINS.get(id(w))
+    if entry is None:
+        return None
+    if not entry.is_current(w):
+        if w.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(
+                "weight twin is stale during graph capture: the weight was "
+                "written by something other than the optimizer step; call "
+                "ops.weight_twin on it (or run one eager step) first")
+        if entry.twin.device != w.device or entry.twin.dtype != w.dtype:
+            entry.twin = w.t().contiguous()
+        else:
+            entry.twin.copy_(w.t())
+        entry.mark_current(w)
+    return entry.twin
+
+
+def invalidate_weight_twin(w: torch.Tensor) -> None:
+    """Mark the twin of `w` stale after a write that neither bumped
+    `w._version` nor moved its storage."""
+    entry = _WEIGHT_TWINS.get(id(w))
+    if entry is not None:
+        entry.version = -1
+
+
+def weight_twin_written(w: torch.Tensor) -> None:
+    """The twin of `w` was just written together with `w` by an op that
+    does not bump `w._version` (fused_adamw): record that it is current."""
+    entry = _WEIGHT_TWINS.get(id(w))
+    if entry is not None:
+        entry.mark_current(w)
+
+
+def valid_weight_twin(w: torch.Tensor) -> Optional[torch.Tensor]:
+    """The twin a dX GEMM should read in place of `w`: :func:`weight_twin`,
+    or None when global_config.weight_twin is off.  The optimizer keeps the
+    twin up whatever the switch says, so it can be flipped at any time."""
+    from ..global_env import global_config
+    return weight_twin(w) if global_config.weight_twin else None
 
 
 # ------------------------------- MoE routing -------------------------------

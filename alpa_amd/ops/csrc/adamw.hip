@@ -10,11 +10,37 @@
 // leaves one scalar on the device and the update derives its clip
 // coefficient from it, so clipping costs one extra read of the gradients
 // and no write pass.
+//
+// Weight twins.  A 2-D bf16 tensor may carry a twin: a second bf16 buffer
+// [cols, rows] that holds the transpose of the updated parameter, which the
+// linear layers' dX GEMM reads in the K-contiguous layout hipBLASLt is
+// fastest at.  Such a tensor is cut into ADAM_TILE x ADAM_TILE tiles, one
+// workgroup each, in place of the flat chunks: the workgroup updates its
+// tile row by row with the same 16-byte accesses, parks the new bf16 values
+// in LDS and writes them out again along the twin's rows, so that the twin
+// costs its own 2 B per element of stores and no extra read or launch.
+//
+// LDS argument for the tile.  A tile row is ADAM_TILE_RS = 33 dwords, an odd
+// count (bank = dword mod 64):
+//   - the transposed read: a lane takes one tile column c and 8 consecutive
+//     tile rows, lane = 8 * (c mod 8) + row group.  For the j-th row of all
+//     groups the 8 row groups are 8 * 33 dwords apart, i.e. 8 distinct
+//     multiples of 8 mod 64, and the 8 columns of a wave add c / 2 in 0..3:
+//     32 distinct banks, each read by the two lanes that share its dword
+//     (a broadcast).  Conflict-free;
+//   - the row-wise store: 4 dwords per lane at 33 * row + 4 * col group.
+//     A row of 33 dwords cannot hold 16-byte-aligned fragments, so these
+//     are ds_write_b32, and rows 4 apart overlap in banks (2-way).  They
+//     are 4 B per element of LDS traffic in a kernel that moves 24 B per
+//     element to and from HBM.
 #include "common.h"
 #include "launchers.h"
 
 #define ADAM_CHUNK 16384
 #define ADAM_BLOCK 256
+
+#define ADAM_TILE 64  // must match _ADAM_TILE in ops/__init__.py
+#define ADAM_TILE_RS (ADAM_TILE / 2 + 1)  // LDS tile row, in dwords
 
 struct AdamTensorDesc {
   void* p;
@@ -24,12 +50,116 @@ struct AdamTensorDesc {
   int64_t numel;
   int32_t is_bf16;  // dtype of p/g
   int32_t _pad;
+  void* twin;  // bf16 [cols, rows], or null: flat chunks
+  int32_t rows;  // p is [rows, cols]; read only with a twin
+  int32_t cols;
 };
 
 struct AdamChunk {
   int32_t tensor_idx;
-  int32_t chunk_idx;  // offset = chunk_idx * ADAM_CHUNK
+  // flat: offset = chunk_idx * ADAM_CHUNK.  With a twin: the tile index,
+  // row-major over the (rows / ADAM_TILE) x (cols / ADAM_TILE) tiles
+  int32_t chunk_idx;
 };
+
+struct AdamCoef {
+  float lr, beta1, beta2, eps, bc1, bc2, wd_factor, grad_scale;
+};
+
+// The update of one element: the only definition, shared by the flat vector
+// loop, the one-element loop and the tiled path, so that which path a tensor
+// takes cannot change its values.  g is the raw gradient.
+//   m = m * beta1 + g * (1 - beta1)
+//   v = v * beta2 + g * g * (1 - beta2)
+//   p = p * wd_factor - lr * (m / bc1) / (sqrt(v / bc2) + eps)
+// Each line holds one fused multiply-add, and the compiler was free to fuse
+// either product of the m and v lines: it fused m * beta1 in the vector loop
+// and g * (1 - beta1) in the one-element loop, so the two differed in the
+// last bit.  The fusions are therefore spelled out, as the vector loop had
+// them (the path every aligned tensor takes), and nothing else may contract.
+__device__ __forceinline__ void adam_element(float g, float& p, float& m,
+                                             float& v, const AdamCoef& k) {
+#pragma clang fp contract(off)
+  g = g * k.grad_scale;
+  m = __builtin_fmaf(m, k.beta1, g * (1.0f - k.beta1));
+  v = __builtin_fmaf(v, k.beta2, (g * g) * (1.0f - k.beta2));
+  const float upd = (k.lr * (m / k.bc1)) / (sqrtf(v / k.bc2) + k.eps);
+  p = __builtin_fmaf(p, k.wd_factor, -upd);
+}
+
+// 8 consecutive elements of bf16 p/g and fp32 m/v at element offset i:
+// 16-byte accesses on p, m and v; on g too when g16, element loads
+// otherwise (a bucket view at an odd element offset).  Returns the updated
+// bf16 values, which are also stored to p.
+__device__ __forceinline__ bf16x8 adam_update8_bf16(const AdamTensorDesc& d,
+                                                    int64_t i, bool g16,
+                                                    const AdamCoef& k) {
+  const short* gp = (const short*)d.g + i;
+  bf16x8 gv;
+  if (g16) {
+    gv = *reinterpret_cast<const bf16x8*>(gp);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) gv[j] = gp[j];
+  }
+  bf16x8 pv = *reinterpret_cast<const bf16x8*>((const short*)d.p + i);
+  f32x4 m0 = *reinterpret_cast<f32x4*>(d.m + i);
+  f32x4 m1 = *reinterpret_cast<f32x4*>(d.m + i + 4);
+  f32x4 v0 = *reinterpret_cast<f32x4*>(d.v + i);
+  f32x4 v1 = *reinterpret_cast<f32x4*>(d.v + i + 4);
+  float m[8] = {m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+  float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+  bf16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float p = bf2f(pv[j]);
+    adam_element(bf2f(gv[j]), p, m[j], v[j], k);
+    o[j] = f2bf(p);
+  }
+  *reinterpret_cast<f32x4*>(d.m + i) = f32x4{m[0], m[1], m[2], m[3]};
+  *reinterpret_cast<f32x4*>(d.m + i + 4) = f32x4{m[4], m[5], m[6], m[7]};
+  *reinterpret_cast<f32x4*>(d.v + i) = f32x4{v[0], v[1], v[2], v[3]};
+  *reinterpret_cast<f32x4*>(d.v + i + 4) = f32x4{v[4], v[5], v[6], v[7]};
+  *reinterpret_cast<bf16x8*>((short*)d.p + i) = o;
+  return o;
+}
+
+// One ADAM_TILE x ADAM_TILE tile of a tensor with a twin (see the header).
+// p, m, v and twin are 16-byte aligned and rows, cols multiples of
+// ADAM_TILE (checked on the host), so every access stays inside the tensor.
+__device__ __forceinline__ void adam_tile(const AdamTensorDesc& d, int tile,
+                                          const AdamCoef& k) {
+  __shared__ uint32_t lds[ADAM_TILE * ADAM_TILE_RS];
+  const int tiles_c = d.cols / ADAM_TILE;
+  const int64_t r0 = (int64_t)(tile / tiles_c) * ADAM_TILE;
+  const int64_t c0 = (int64_t)(tile % tiles_c) * ADAM_TILE;
+  const bool g16 = (((uintptr_t)d.g) & 15) == 0;
+  const int t = threadIdx.x;
+  // 8 lanes cover one 64-element row; 256 threads cover 32 rows a trip
+#pragma unroll
+  for (int r = t / 8; r < ADAM_TILE; r += ADAM_BLOCK / 8) {
+    const int cg = t % 8;
+    bf16x8 o = adam_update8_bf16(d, (r0 + r) * d.cols + c0 + cg * 8, g16, k);
+    uint32_t* dst = lds + r * ADAM_TILE_RS + cg * 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      dst[j] = (uint32_t)(uint16_t)o[2 * j] |
+               ((uint32_t)(uint16_t)o[2 * j + 1] << 16);
+  }
+  __syncthreads();
+  // twin row c0 + c, columns r0 + 8 * rg .. + 8: 8 lanes store 128 B of it
+  const short* lds16 = (const short*)lds;
+#pragma unroll
+  for (int c = t / 8; c < ADAM_TILE; c += ADAM_BLOCK / 8) {
+    const int rg = t % 8;
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      o[j] = lds16[(rg * 8 + j) * (2 * ADAM_TILE_RS) + c];
+    *reinterpret_cast<bf16x8*>((short*)d.twin + (c0 + c) * d.rows + r0 +
+                               rg * 8) = o;
+  }
+}
 
 __global__ void adamw_kernel(const AdamTensorDesc* __restrict__ descs,
                              const AdamChunk* __restrict__ chunks,
@@ -57,30 +187,14 @@ __global__ void adamw_kernel(const AdamTensorDesc* __restrict__ descs,
   }
   AdamChunk c = chunks[cid];
   AdamTensorDesc d = descs[c.tensor_idx];
+  const AdamCoef k = {lr,  beta1, beta2, eps,
+                      bc1, bc2,   1.0f - lr * weight_decay, grad_scale};
+  if (d.twin != nullptr) {
+    adam_tile(d, c.chunk_idx, k);
+    return;
+  }
   int64_t base = (int64_t)c.chunk_idx * ADAM_CHUNK;
   int64_t end = min(base + ADAM_CHUNK, d.numel);
-
-  const float wd_factor = 1.0f - lr * weight_decay;
-  // one element, all dtypes: the tail after the vector loop, and every
-  // element of a tensor that cannot take the vector loop
-  auto scalar_update = [&](int64_t i) {
-    float g, p;
-    if (d.is_bf16) {
-      g = bf2f(((const short*)d.g)[i]) * grad_scale;
-      p = bf2f(((const short*)d.p)[i]);
-    } else {
-      g = ((const float*)d.g)[i] * grad_scale;
-      p = ((const float*)d.p)[i];
-    }
-    float m = d.m[i] = d.m[i] * beta1 + g * (1.0f - beta1);
-    float v = d.v[i] = d.v[i] * beta2 + g * g * (1.0f - beta2);
-    p = p * wd_factor;
-    p -= lr * (m / bc1) / (sqrtf(v / bc2) + eps);
-    if (d.is_bf16)
-      ((short*)d.p)[i] = f2bf(p);
-    else
-      ((float*)d.p)[i] = p;
-  };
 
   // The vector loop moves 16 B per access and needs all four streams
   // 16B-aligned (chunk bases are multiples of ADAM_CHUNK and keep the
@@ -96,59 +210,49 @@ __global__ void adamw_kernel(const AdamTensorDesc* __restrict__ descs,
   const int64_t n_full = vec ? (end - base) / 8 * 8 : 0;
   for (int64_t i = base + (int64_t)threadIdx.x * 8; i < base + n_full;
        i += (int64_t)ADAM_BLOCK * 8) {
-    float g[8], p[8];
     if (d.is_bf16) {
-      bf16x8 gv = *reinterpret_cast<const bf16x8*>((const short*)d.g + i);
-      bf16x8 pv = *reinterpret_cast<const bf16x8*>((const short*)d.p + i);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        g[j] = bf2f(gv[j]) * grad_scale;
-        p[j] = bf2f(pv[j]);
-      }
-    } else {
-      f32x4 g0 = *reinterpret_cast<const f32x4*>((const float*)d.g + i);
-      f32x4 g1 = *reinterpret_cast<const f32x4*>((const float*)d.g + i + 4);
-      f32x4 p0 = *reinterpret_cast<const f32x4*>((const float*)d.p + i);
-      f32x4 p1 = *reinterpret_cast<const f32x4*>((const float*)d.p + i + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        g[j] = g0[j] * grad_scale;
-        g[4 + j] = g1[j] * grad_scale;
-        p[j] = p0[j];
-        p[4 + j] = p1[j];
-      }
+      adam_update8_bf16(d, i, true, k);
+      continue;
     }
+    f32x4 g0 = *reinterpret_cast<const f32x4*>((const float*)d.g + i);
+    f32x4 g1 = *reinterpret_cast<const f32x4*>((const float*)d.g + i + 4);
+    f32x4 p0 = *reinterpret_cast<const f32x4*>((const float*)d.p + i);
+    f32x4 p1 = *reinterpret_cast<const f32x4*>((const float*)d.p + i + 4);
     f32x4 m0 = *reinterpret_cast<f32x4*>(d.m + i);
     f32x4 m1 = *reinterpret_cast<f32x4*>(d.m + i + 4);
     f32x4 v0 = *reinterpret_cast<f32x4*>(d.v + i);
     f32x4 v1 = *reinterpret_cast<f32x4*>(d.v + i + 4);
+    float g[8] = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};
+    float p[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
     float m[8] = {m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
     float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      m[j] = m[j] * beta1 + g[j] * (1.0f - beta1);
-      v[j] = v[j] * beta2 + g[j] * g[j] * (1.0f - beta2);
-      p[j] = p[j] * wd_factor - lr * (m[j] / bc1) / (sqrtf(v[j] / bc2) + eps);
-    }
+    for (int j = 0; j < 8; ++j) adam_element(g[j], p[j], m[j], v[j], k);
     *reinterpret_cast<f32x4*>(d.m + i) = f32x4{m[0], m[1], m[2], m[3]};
     *reinterpret_cast<f32x4*>(d.m + i + 4) = f32x4{m[4], m[5], m[6], m[7]};
     *reinterpret_cast<f32x4*>(d.v + i) = f32x4{v[0], v[1], v[2], v[3]};
     *reinterpret_cast<f32x4*>(d.v + i + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    if (d.is_bf16) {
-      bf16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = f2bf(p[j]);
-      *reinterpret_cast<bf16x8*>((short*)d.p + i) = o;
-    } else {
-      *reinterpret_cast<f32x4*>((float*)d.p + i) =
-          f32x4{p[0], p[1], p[2], p[3]};
-      *reinterpret_cast<f32x4*>((float*)d.p + i + 4) =
-          f32x4{p[4], p[5], p[6], p[7]};
-    }
+    *reinterpret_cast<f32x4*>((float*)d.p + i) =
+        f32x4{p[0], p[1], p[2], p[3]};
+    *reinterpret_cast<f32x4*>((float*)d.p + i + 4) =
+        f32x4{p[4], p[5], p[6], p[7]};
   }
-  // scalar tail (final partial 8-group of the tensor's last chunk)
-  for (int64_t i = base + n_full + threadIdx.x; i < end; i += ADAM_BLOCK)
-    scalar_update(i);
+  // one element at a time: the final partial 8-group of the tensor's last
+  // chunk, and every element of a tensor that cannot take the vector loop
+  for (int64_t i = base + n_full + threadIdx.x; i < end; i += ADAM_BLOCK) {
+    float p = d.is_bf16 ? bf2f(((const short*)d.p)[i])
+                        : ((const float*)d.p)[i];
+    float g = d.is_bf16 ? bf2f(((const short*)d.g)[i])
+                        : ((const float*)d.g)[i];
+    float m = d.m[i], v = d.v[i];
+    adam_element(g, p, m, v, k);
+    d.m[i] = m;
+    d.v[i] = v;
+    if (d.is_bf16)
+      ((short*)d.p)[i] = f2bf(p);
+    else
+      ((float*)d.p)[i] = p;
+  }
 }
 
 // ------------------------- gradient sum of squares -------------------------

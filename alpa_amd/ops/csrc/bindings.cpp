@@ -503,16 +503,50 @@ at::Tensor skinny_gemm_mfma_fp4(const at::Tensor& wq, const at::Tensor& sq,
 
 // -------------------------------- AdamW ----------------------------------
 
+constexpr int64_t ADAM_TILE = 64;      // ADAM_TILE in adamw.hip
+constexpr int64_t ADAM_DESC_WORDS = 8;  // sizeof(AdamTensorDesc) / 8
+
+// descs: one AdamTensorDesc per row; chunks: (tensor_idx, chunk_idx)
+void check_adam_tables(const at::Tensor& descs, const at::Tensor& chunks) {
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 2,
+              "chunks must be [m, 2]");
+  check_vec(chunks, "chunks", at::kInt, chunks.numel(), chunks);
+  TORCH_CHECK(descs.dim() == 2 && descs.size(1) == ADAM_DESC_WORDS,
+              "descs must be [n, ", ADAM_DESC_WORDS, "]");
+  check_vec(descs, "descs", at::kLong, descs.numel(), chunks);
+}
+
+// The tables hold raw pointers, so what the tiled path of adamw_kernel asks
+// of a tensor with a twin is checked here, on the tensors, when the table
+// row is built: p bf16 [rows, cols] with both a multiple of ADAM_TILE, twin
+// bf16 [cols, rows], m and v fp32 of p's shape, all four contiguous and
+// 16-byte aligned (g may start at any element).
+void adamw_check_twin(const at::Tensor& p, const at::Tensor& m,
+                      const at::Tensor& v, const at::Tensor& twin) {
+  auto dims = check_aligned_rows(p, "p", p);
+  TORCH_CHECK(dims.first % ADAM_TILE == 0 && dims.second % ADAM_TILE == 0,
+              "p: a tensor with a twin must have rows and cols that are "
+              "multiples of ", ADAM_TILE, ", got [", dims.first, ", ",
+              dims.second, "]");
+  TORCH_CHECK(dims.first <= INT32_MAX && dims.second <= INT32_MAX,
+              "p: rows and cols must fit int32");
+  check_aligned_rows(twin, "twin", p);
+  TORCH_CHECK(twin.size(0) == dims.second && twin.size(1) == dims.first,
+              "twin must be [cols, rows] = [", dims.second, ", ", dims.first,
+              "], got ", twin.sizes());
+  check_vec(m, "m", at::kFloat, p.numel(), p);
+  check_vec(v, "v", at::kFloat, p.numel(), p);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(m.const_data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(v.const_data_ptr()) % 16 == 0,
+              "m and v must be 16-byte aligned");
+}
+
 void adamw_step_raw(const at::Tensor& descs, const at::Tensor& chunks,
                     int64_t step, double lr, double beta1, double beta2,
                     double eps, double weight_decay, double grad_scale,
                     const c10::optional<at::Tensor>& grad_sumsq,
                     double max_grad_norm) {
-  TORCH_CHECK(descs.dim() == 2 && descs.size(1) == 6, "descs must be [n, 6]");
-  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 2,
-              "chunks must be [m, 2]");
-  check_vec(descs, "descs", at::kLong, descs.numel(), descs);
-  check_vec(chunks, "chunks", at::kInt, chunks.numel(), descs);
+  check_adam_tables(descs, chunks);
   const float* sumsq = nullptr;
   if (grad_sumsq.has_value()) {
     check_vec(*grad_sumsq, "grad_sumsq", at::kFloat, 1, descs);
@@ -530,11 +564,7 @@ void adamw_step_raw(const at::Tensor& descs, const at::Tensor& chunks,
 // partials: fp32 workspace [num_chunks]; out: fp32 [1]
 void multi_tensor_sumsq_raw(const at::Tensor& descs, const at::Tensor& chunks,
                             at::Tensor& partials, at::Tensor& out) {
-  TORCH_CHECK(descs.dim() == 2 && descs.size(1) == 6, "descs must be [n, 6]");
-  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 2,
-              "chunks must be [m, 2]");
-  check_vec(descs, "descs", at::kLong, descs.numel(), descs);
-  check_vec(chunks, "chunks", at::kInt, chunks.numel(), descs);
+  check_adam_tables(descs, chunks);
   int64_t n = chunks.size(0);
   // the workspace may be longer than the chunk table
   check_typed(partials, "partials", at::kFloat, descs);
@@ -1361,7 +1391,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // take an optional out_dtype (fp32 or bf16) for the vectors they reduce
   // 10: kv_cache_append and attn_decode_fp8 added (e4m3 KV cache)
   // 11: attn_chunk and attn_chunk_fp8 added (query chunks over a KV cache)
-  m.attr("ABI_VERSION") = 11;
+  // 12: AdamW descriptor rows are 8 words (twin, rows, cols added);
+  // adamw_check_twin added
+  m.attr("ABI_VERSION") = 12;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)",
         py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),
@@ -1394,6 +1426,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("grad_sumsq") = py::none(), py::arg("max_grad_norm") = 0.0);
   m.def("multi_tensor_sumsq_raw", &multi_tensor_sumsq_raw,
         "multi-tensor sum of squares (gfx950)");
+  m.def("adamw_check_twin", &adamw_check_twin,
+        "operand checks for an AdamW tensor with a transposed twin",
+        py::arg("p"), py::arg("m"), py::arg("v"), py::arg("twin"));
   m.def("fp8_quantize", &fp8_quantize,
         "one-pass fp8 amax+cast, optional transposed twin (gfx950)");
   m.def("bias_gelu_fp8", &bias_gelu_fp8,

@@ -386,8 +386,11 @@ def softmax_cross_entropy_shard_bwd(dloss: torch.Tensor, logits: torch.Tensor,
 def adamw_step(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float,
                beta1: float, beta2: float, eps: float, weight_decay: float,
                grad_scale: float = 1.0, grad_sumsq=None,
-               max_grad_norm=None):
+               max_grad_norm=None, twins=None):
     """In-place multi-tensor AdamW (fp32 master math on fp32 state).
+
+    twins, aligned with params, holds None or a [cols, rows] tensor that
+    receives the transpose of the updated [rows, cols] parameter.
 
     With grad_sumsq (a one-element tensor, the sum of squares of all raw
     gradients) and max_grad_norm, the gradients are clipped by global norm
@@ -411,6 +414,7 @@ def adamw_step(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float,
             denom = (v / bc2).sqrt_().add_(eps)
             pf.addcdiv_(m / bc1, denom, value=-lr)
             p.copy_(pf.to(p.dtype))
+        _write_twins(params, twins)
         return
     if not max_grad_norm > 0:
         raise ValueError(f"max_grad_norm must be > 0, got {max_grad_norm}")
@@ -429,6 +433,14 @@ def adamw_step(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float,
         m.copy_(torch.where(ok, m_new, m))
         v.copy_(torch.where(ok, v_new, v))
         p.copy_(torch.where(ok, pf.to(p.dtype), p))
+    # p is unchanged on a non-finite norm, and then so is its transpose
+    _write_twins(params, twins)
+
+
+def _write_twins(params, twins):
+    for p, t in zip(params, twins or ()):
+        if t is not None:
+            t.copy_(p.t())
 
 
 def multi_tensor_sumsq(tensors) -> torch.Tensor:

@@ -56,6 +56,11 @@ class AdamW:
     sharded instead of replicated (expert-parallel weights): the squares of
     those gradients are summed over the group, all others count once, so
     every rank clips by the same global norm.
+
+    `attach_weight_twins(model)` makes this optimizer maintain the
+    transposed copies of the linear weights that their dX GEMMs read
+    (ops.weight_twin): the fused kernel writes each one next to its
+    parameter, in the same launch.  Without that call nothing is allocated.
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-4,
@@ -74,6 +79,8 @@ class AdamW:
         self.eps = eps
         self.weight_decay = weight_decay
         self.step_count = 0
+        #: id(param) -> its twin (attach_weight_twins)
+        self._twins: dict = {}
         self.exp_avgs = [
             torch.zeros(p.shape, dtype=torch.float32, device=p.device)
             for p in self.params
@@ -82,6 +89,55 @@ class AdamW:
             torch.zeros(p.shape, dtype=torch.float32, device=p.device)
             for p in self.params
         ]
+
+    #: twins are attached only if all of them together take at most this
+    #: fraction of the device's memory (9 GB of 288): GPT-2.6B's 5.3 GB
+    #: is the one size whose step was measured with twins.  GPT-15B's
+    #: 30 GB is what docs/BENCHMARK.md ("fp8 GEMM mode") records as enough
+    #: to make hipGraph capture run out of memory there, so larger models
+    #: keep dX on the weight until their headroom has been measured.
+    TWIN_MEMORY_FRACTION = 1.0 / 32
+
+    @torch.no_grad()
+    def attach_weight_twins(self, model: torch.nn.Module) -> int:
+        """Register a twin for the weight of every ColumnParallelLinear /
+        RowParallelLinear of `model` that this optimizer updates and that
+        is eligible (ops.weight_twin_eligible), the LM head included,
+        except weights shared with another module (tied embeddings).
+        All or nothing, and nothing when global_config.weight_twin is off,
+        when global_config.fp8_gemm is on (those layers' backward runs in
+        ops/fp8.py and never reads a twin) or when the twins would take
+        more than TWIN_MEMORY_FRACTION of the GPU's memory.  Returns how
+        many it holds."""
+        from .global_env import global_config
+        from .parallel.layers import ColumnParallelLinear, RowParallelLinear
+        if not global_config.weight_twin or global_config.fp8_gemm:
+            return 0
+        mine = {id(p) for p in self.params}
+        uses = {}
+        for mod in model.modules():
+            w = getattr(mod, "weight", None)
+            if isinstance(w, torch.nn.Parameter):
+                uses[id(w)] = uses.get(id(w), 0) + 1
+        todo = []
+        for mod in model.modules():
+            if not isinstance(mod, (ColumnParallelLinear, RowParallelLinear)):
+                continue
+            w = mod.weight
+            if id(w) in mine and uses[id(w)] == 1 \
+                    and id(w) not in self._twins \
+                    and ops.weight_twin_eligible(w):
+                todo.append(w)
+        on_gpu = [w for w in todo if w.is_cuda]
+        if on_gpu:
+            need = sum(w.numel() * w.element_size() for w in on_gpu)
+            total = torch.cuda.get_device_properties(
+                on_gpu[0].device).total_memory
+            if need > self.TWIN_MEMORY_FRACTION * total:
+                return len(self._twins)
+        for w in todo:
+            self._twins[id(w)] = ops.register_weight_twin(w)
+        return len(self._twins)
 
     @torch.no_grad()
     def step(self, grads: Optional[List[torch.Tensor]] = None,
@@ -104,10 +160,19 @@ class AdamW:
             if grad_sumsq is None:
                 grad_sumsq = self._global_sumsq(ps, gs)
             self.last_grad_norm = global_grad_norm(grad_sumsq, grad_scale)
+        twins = None
+        if self._twins:
+            # a twin that another writer left stale is rebuilt first, so
+            # that a skipped update (non-finite norm) still leaves it right
+            twins = [ops.weight_twin(p) if id(p) in self._twins
+                     else None for p in ps]
         ops.fused_adamw(ps, gs, ms, vs, self.step_count, self.lr,
                         self.beta1, self.beta2, self.eps,
                         self.weight_decay, grad_scale, grad_sumsq,
-                        self.max_grad_norm)
+                        self.max_grad_norm, twins)
+        if twins is not None:
+            for p in ps:
+                ops.weight_twin_written(p)
 
     def _global_sumsq(self, ps, gs) -> torch.Tensor:
         """Sum of squares of the model's gradients: the replicated ones

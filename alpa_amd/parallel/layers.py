@@ -205,12 +205,12 @@ class ColumnParallelLinear(nn.Module):
             return fp8_linear(x, self.weight, self.bias, module=self)
         if self.gelu:
             assert self.bias is not None
-            pre = torch.matmul(x, self.weight.t())
+            pre = ops.linear_bias(x, self.weight, None)
             return pre if defer_gelu else ops.bias_gelu(pre, self.bias)
         if self.bias is not None:
             # bias fused into the hipBLASLt epilogue (addmm)
             return ops.linear_bias(x, self.weight, self.bias)
-        return torch.matmul(x, self.weight.t())
+        return ops.linear_bias(x, self.weight, None)
 
     def _use_fp8(self, x):
         return _fp8_ok(x, self.weight, self)
@@ -287,7 +287,7 @@ class RowParallelLinear(nn.Module):
             # bias fuses into the hipBLASLt epilogue
             return ops.linear_bias(x, self.weight, self.bias)
         else:
-            y = torch.matmul(x, self.weight.t())
+            y = ops.linear_bias(x, self.weight, None)
         y = reduce_from_tp(y, self.mesh, self.axis)
         if self.bias is not None:
             y = ops.bias_add(y, self.bias)  # after the tp all-reduce

@@ -15,8 +15,9 @@ __version__ = "0.1.0"
 #: of LayerNorm, bias+GeLU and the bias column sum take the out_dtype that
 #: every autograd function passes; 10: kv_cache_append and attn_decode_fp8,
 #: the e4m3 KV cache; 11: attn_chunk and attn_chunk_fp8, query chunks over a
-#: KV cache)
-MIN_HIP_OPS_ABI = 11
+#: KV cache; 12: 8-word AdamW descriptor rows with the twin fields, and
+#: adamw_check_twin)
+MIN_HIP_OPS_ABI = 12
 
 
 def check_hip_ops_version() -> int:
