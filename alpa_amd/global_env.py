@@ -130,6 +130,38 @@ class GlobalConfig:
     kv_cache_fp8: bool = field(
         default_factory=lambda: _env_bool("ALPA_AMD_KV_FP8", False))
 
+    #: one kernel (ops/csrc/qkv_cache_write.hip, ops.qkv_cache_write) for
+    #: what a cached decoder step does between its qkv projection and its
+    #: attention kernel: the q/k/v split, CodeGen's rotary transform of q
+    #: and k, q made contiguous, and the write of k and v into the bf16 or
+    #: e4m3 KV cache at per-slot positions read on the device.  Taken by
+    #: DecoderBlock._attn on every cached call inside
+    #: ops.qkv_cache_write_ok; training and the CPU keep the torch ops.  It
+    #: is what gives CodeGen per-slot positions (forward_decode,
+    #: generate_graphed).  For OPT and BLOOM it moves the same bits as the
+    #: torch ops; for CodeGen the rotation is done in fp32 and rounded once
+    #: where apply_rotary rounds to bf16 after every op.
+    #: Rule: every shape class takes the kernel, because none measured
+    #: slower than the torch ops beyond the repeat-to-repeat spread
+    #: (tools/qkv_cache_bench.py on one MI355X, table in docs/BENCHMARK.md,
+    #: "Fused qkv split, rotary and cache write"; us per call, torch ->
+    #: fused, spread <= 0.05 eager and <= 0.18 graphed).  CodeGen-16B heads,
+    #: decode at batch 1-32: 124-127 -> 19.6-20.8 eager, 44-50 -> 3.2-4.4
+    #: inside a captured graph; 2048-token prefill 181 -> 25 (bf16 cache),
+    #: 176 -> 36 (e4m3).  OPT-13B heads, per-slot positions: 30 -> 19 eager
+    #: and 11-13 -> 2.3-2.4 graphed (bf16 cache), 24 -> 19-20 eager and
+    #: 5.1-5.3 -> 3.1-3.3 graphed (e4m3, against the one-launch append);
+    #: prefill 52 -> 20 and 38 -> 25.  The eager figures are host time: one
+    #: dispatch plus the envelope check.  End to end (serve_bench, prompt
+    #: 128, batch 8, two alternating repeats): CodeGen-16B 11.52 / 11.87 ->
+    #: 9.71 / 9.69 ms/token eager and 9.77 / 9.79 graphed (no graphed loop
+    #: without the kernel); OPT-13B 9.16 / 9.27 -> 8.96 / 8.97 eager, 9.71 /
+    #: 9.71 -> 9.10 / 9.11 graphed.
+    #: "1" (default) on; ALPA_AMD_FUSED_QKV=0 restores the torch ops (and
+    #: with them CodeGen's refusal of per-slot positions).
+    fused_qkv_write: str = field(
+        default_factory=lambda: os.environ.get("ALPA_AMD_FUSED_QKV", "1"))
+
     #: bf16 dX GEMMs of the parallel linear layers read a transposed copy
     #: of the weight (its "twin", ops.weight_twin) that the fused AdamW
     #: kernel writes next to the weight: dY @ W (NN) becomes the TN GEMM

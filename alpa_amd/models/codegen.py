@@ -6,8 +6,14 @@ ONE LayerNorm feeding attention AND the MLP in parallel
 (x + attn(ln(x)) + mlp(ln(x))), rotary embedding applied to the first
 ``rotary_dim`` dims of every head (interleaved/"rotate_every_two"
 convention).  Rotary is an elementwise pre-transform of q/k, so the
-unmodified gfx950 flash-attention kernel serves both prefill and cached
-decode; generation (greedy + beam) comes from GenerationMixin.
+unmodified gfx950 attention kernels serve prefill and cached decode.  On the
+GPU a cached call rotates inside ops.qkv_cache_write, the kernel that also
+splits the packed qkv and writes the KV cache: it reads per-slot positions on
+the device, so CodeGen runs under continuous batching (forward_decode) and
+the hipGraph-captured decode loop (generate_graphed) like OPT and BLOOM.
+Training, the CPU and calls outside that kernel's envelope rotate with
+apply_rotary, which takes one int position for the whole batch.  Generation
+(greedy + beam) comes from GenerationMixin.
 """
 from __future__ import annotations
 
@@ -101,14 +107,19 @@ class CodeGenModel(CachedDecoder):
         return self.wte(ids)
 
     def _rotate(self, x, pos):
+        """The torch rotary of the calls that ops.qkv_cache_write does not
+        take (training, CPU, outside its envelope)."""
         if not isinstance(pos, int):
             raise NotImplementedError(
                 "CodeGen rotary takes one int position for the whole batch; "
                 "per-slot positions (forward_decode, continuous batching) "
-                "are not implemented")
+                "are implemented by ops.qkv_cache_write on the GPU only")
         return apply_rotary(x, self.rot_sin, self.rot_cos, pos,
                             self.cfg.rotary_dim)
 
     def _attn_args(self):
-        return {"rotate": self._rotate}
+        """The rotary transform in both forms DecoderBlock._attn takes: the
+        torch callable and the tables of the fused kernel."""
+        return {"rotate": self._rotate,
+                "rotary": (self.rot_sin, self.rot_cos, self.cfg.rotary_dim)}
 

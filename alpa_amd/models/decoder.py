@@ -97,6 +97,55 @@ class KVCache:
         return self.k[i], self.v[i]
 
 
+def _fused_write_routed(qkv, cache_k, cache_v, pos, rotary) -> bool:
+    """Does this cached call take ops.qkv_cache_write?  The switch, its
+    rule and the measurements behind it are on
+    global_config.fused_qkv_write."""
+    from ..global_env import global_config
+    if global_config.fused_qkv_write in ("0", False) or \
+            torch.is_grad_enabled() and qkv.requires_grad:
+        return False
+    return ops.qkv_cache_write_ok(qkv, cache_k, cache_v, pos, rotary)
+
+
+def split_qkv_into_cache(qkv, cache_k, cache_v, pos, rotate=None,
+                         rotary=None):
+    """What a block does between its qkv projection and its attention call:
+    qkv [B, S, h, 3, d] (the packed projection) -> (q, k, v) as [B, h, S, d],
+    q and k rotated and q contiguous, with k and v written at positions
+    pos_b .. pos_b + S - 1 of the cache (cache_k None: no cache).  `rotate`
+    and `rotary` are the family's rotary transform in two forms: a callable
+    (x, pos) -> rotated, and the (sin, cos, rotary_dim) of
+    ops.qkv_cache_write.  A cached call inside that kernel's envelope
+    (global_config.fused_qkv_write) is its one launch; every other call is
+    the torch ops below."""
+    B, S = qkv.shape[:2]
+    q, k, v = (qkv[:, :, :, i].permute(0, 2, 1, 3) for i in range(3))
+    fp8 = isinstance(cache_k, tuple)
+    if cache_k is not None and _fused_write_routed(qkv, cache_k, cache_v,
+                                                   pos, rotary):
+        # the e4m3 prefill attends over the fresh k: ask for it
+        want_k = fp8 and S > 1 and pos == 0
+        out = ops.qkv_cache_write(qkv, cache_k, cache_v, pos, rotary,
+                                  want_k=want_k, _in_envelope=True)
+        return (*out, v) if want_k else (out, k, v)
+    if rotate is not None:
+        q, k = rotate(q, pos), rotate(k, pos)
+    q = q.contiguous()
+    if fp8:
+        (k8, ks), (v8, vs) = cache_k, cache_v
+        ops.kv_cache_append_fp8(k, v, k8, ks, v8, vs, pos)
+    elif cache_k is not None and isinstance(pos, int):
+        cache_k[:, :, pos:pos + S] = k
+        cache_v[:, :, pos:pos + S] = v
+    elif cache_k is not None:
+        assert S == 1
+        bidx = torch.arange(B, device=qkv.device)
+        cache_k[bidx, :, pos] = k[:, :, 0]
+        cache_v[bidx, :, pos] = v[:, :, 0]
+    return q, k, v
+
+
 class DecoderBlock(nn.Module):
     """Attention + MLP block.  `gelu`: fc1 fuses bias+GeLU (BLOOM, CodeGen)
     instead of a relu after a plain fc1 (OPT).  `parallel`: one LayerNorm
@@ -129,7 +178,8 @@ class DecoderBlock(nn.Module):
                           gelu=gelu)
         self.fc2 = linear(RowParallelLinear, ffn, hidden, "fc2")
 
-    def _attn(self, x, cache_k, cache_v, pos, slopes, rotate, cap):
+    def _attn(self, x, cache_k, cache_v, pos, slopes, rotate, cap,
+              rotary=None):
         """pos: int — all rows sit at pos..pos+S-1 (prefill, lock-step
         decode); LongTensor [B] — one token per slot at its own position
         (continuous batching), attended with kv_lens = pos + 1.  `cap`
@@ -137,14 +187,13 @@ class DecoderBlock(nn.Module):
         host-synced pos.max() — required under hipGraph capture (the
         varlen kernel masks past each slot's device-side length anyway).
         cache_k None: no cache, causal over the block's own k/v (training;
-        cache writes are no-grad buffers and would detach k/v)."""
+        cache writes are no-grad buffers and would detach k/v).  `rotate`
+        and `rotary`: split_qkv_into_cache, which has written the cache
+        when the attention calls below read it."""
         B, S, _ = x.shape
         h, d = self.heads_per_rank, self.head_dim
-        qkv = self.qkv(x).view(B, S, h, 3, d)
-        q, k, v = (qkv[:, :, :, i].permute(0, 2, 1, 3) for i in range(3))
-        if rotate is not None:
-            q, k = rotate(q, pos), rotate(k, pos)
-        q = q.contiguous()
+        q, k, v = split_qkv_into_cache(self.qkv(x).view(B, S, h, 3, d),
+                                       cache_k, cache_v, pos, rotate, rotary)
         if isinstance(cache_k, tuple):
             o = self._attn_fp8(q, k, v, cache_k, cache_v, pos, slopes, cap)
         elif cache_k is None:
@@ -152,8 +201,6 @@ class DecoderBlock(nn.Module):
                                     causal=True, alibi_slopes=slopes)
         elif isinstance(pos, int):
             total = pos + S
-            cache_k[:, :, pos:total] = k
-            cache_v[:, :, pos:total] = v
             if pos > 0 and S > 1:
                 # a chunk with history: causal at the end of the cache
                 o = ops.flash_attention_chunk(q, cache_k[:, :, :total],
@@ -165,10 +212,6 @@ class DecoderBlock(nn.Module):
                                         cache_v[:, :, :total], causal=S > 1,
                                         alibi_slopes=slopes)
         else:
-            assert S == 1
-            bidx = torch.arange(B, device=x.device)
-            cache_k[bidx, :, pos] = k[:, :, 0]
-            cache_v[bidx, :, pos] = v[:, :, 0]
             total = cap or int(pos.max()) + 1
             o = ops.flash_attention_varlen(q, cache_k[:, :, :total],
                                            cache_v[:, :, :total], pos + 1,
@@ -176,17 +219,16 @@ class DecoderBlock(nn.Module):
         return self.out(o.permute(0, 2, 1, 3).reshape(B, S, h * d))
 
     def _attn_fp8(self, q, k, v, cache_k, cache_v, pos, slopes, cap):
-        """The cached branches of _attn over an e4m3 cache: cache_k and
-        cache_v are (bytes, scales).  Prefill attends over the fresh bf16
-        k/v, which is all there is to see at pos == 0, and then appends;
-        a chunk with history appends first and reads the cache through the
-        e4m3 chunk kernel; a single-token step appends first and reads the
-        cache through the e4m3 decode kernel with kv_lens = pos + 1."""
+        """The cached branches of _attn over an e4m3 cache that already holds
+        the new rows: cache_k and cache_v are (bytes, scales).  Prefill
+        attends over the fresh bf16 k/v, which is all there is to see at
+        pos == 0; a chunk with history reads the cache through the e4m3
+        chunk kernel; a single-token step reads it through the e4m3 decode
+        kernel with kv_lens = pos + 1."""
         (k8, ks), (v8, vs) = cache_k, cache_v
         B, S = q.shape[0], q.shape[2]
         if S > 1:
             assert isinstance(pos, int)
-            ops.kv_cache_append_fp8(k, v, k8, ks, v8, vs, pos)
             if pos == 0:
                 return ops.flash_attention(q, k.contiguous(), v.contiguous(),
                                            causal=True, alibi_slopes=slopes)
@@ -194,7 +236,6 @@ class DecoderBlock(nn.Module):
             return ops.flash_attention_chunk_fp8(
                 q, k8[:, :, :total], ks[:, :, :total], v8[:, :, :total],
                 vs[:, :, :total], alibi_slopes=slopes)
-        ops.kv_cache_append_fp8(k, v, k8, ks, v8, vs, pos)
         if isinstance(pos, int):
             total, lens = pos + 1, None
         else:
@@ -208,13 +249,13 @@ class DecoderBlock(nn.Module):
         return self.fc2(y if self.gelu else torch.nn.functional.relu(y))
 
     def forward(self, x, cache_k, cache_v, pos, slopes=None, rotate=None,
-                cap=None):
+                cap=None, rotary=None):
         if self.parallel:
             y = self.ln(x)
             return x + self._attn(y, cache_k, cache_v, pos, slopes, rotate,
-                                  cap) + self._mlp(y)
+                                  cap, rotary) + self._mlp(y)
         x = x + self._attn(self.ln1(x), cache_k, cache_v, pos, slopes,
-                           rotate, cap)
+                           rotate, cap, rotary)
         return x + self._mlp(self.ln2(x))
 
 
@@ -264,7 +305,8 @@ class CachedDecoder(nn.Module, GenerationMixin):
         raise NotImplementedError
 
     def _attn_args(self) -> dict:
-        """Per-call keyword arguments of the blocks (slopes, rotate)."""
+        """Per-call keyword arguments of the blocks (slopes, rotate,
+        rotary)."""
         return {}
 
     def _run_blocks(self, x, cache, pos, cap=None):

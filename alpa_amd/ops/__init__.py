@@ -20,7 +20,13 @@ cached row), which global_config.kv_cache_fp8 turns on in the decoders.
 flash_attention_chunk and flash_attention_chunk_fp8 are the split-KV MFMA
 kernel for several query rows over a cache that already holds them (chunked
 prefill, draft verification, a multi-token turn), causal at the end of the
-cache.  skinny_ok / skinny_linear are the packed decode GEMMs for up to 64
+cache.  qkv_cache_write is what runs between the qkv projection and those
+attention kernels in a cached decoder step, as one kernel: it splits the
+packed projection, applies the rotary transform to q and k (CodeGen), writes
+q contiguous and writes k and v into the bf16 or e4m3 cache at per-slot
+positions read on the device (global_config.fused_qkv_write;
+qkv_cache_write_ok is its envelope).  skinny_ok / skinny_linear are the
+packed decode GEMMs for up to 64
 tokens (dot2 GEMV up to 8, MFMA skinny GEMM for 9..64) over bf16, e4m3 or,
 under global_config.weight_fp4, MXFP4 weights: mxfp4_quantize and
 mxfp4_dequantize are that format (e2m1 codes, one e8m0 scale per 32 k),
@@ -48,7 +54,8 @@ __all__ = [
     "layer_norm", "add_layer_norm", "bias_gelu", "add_layer_norm_fp8",
     "bias_gelu_fp8", "flash_attention",
     "flash_attention_qkv", "flash_attention_decode", "decode_attn_ok",
-    "DECODE_ATTN_CHUNK", "kv_cache_append_fp8",
+    "DECODE_ATTN_CHUNK", "kv_cache_append_fp8", "qkv_cache_write",
+    "qkv_cache_write_ok",
     "flash_attention_decode_fp8", "decode_attn_fp8_ok",
     "flash_attention_chunk", "chunk_attn_ok", "flash_attention_chunk_fp8",
     "chunk_attn_fp8_ok",
@@ -558,6 +565,102 @@ def kv_cache_append_fp8(k: torch.Tensor, v: torch.Tensor, k8: torch.Tensor,
                                       int(pos), None)
         return
     ref.kv_cache_append_fp8(k, v, k8, k_scale, v8, v_scale, pos)
+
+
+def qkv_cache_write_ok(qkv: torch.Tensor, cache_k, cache_v, pos,
+                       rotary) -> bool:
+    """Envelope of csrc/qkv_cache_write.hip (the binding checks the same):
+    qkv a bf16 [B, S, h, 3, d] view on the GPU with stride(4) == 1,
+    stride(3) == d, B/S/h strides that are multiples of 8 elements and a
+    16-byte-aligned base, d a multiple of 16 in [16, 256]; cache_k and cache_v
+    what KVCache.layer returns: bf16 [B, h, L, d] views with a contiguous head
+    dim and 16-byte-aligned rows, or (bytes, scales) pairs inside
+    _kv8_ok(.., 8); pos an int or a contiguous int32/int64 [B] on the device;
+    rotary None or (sin, cos, rotary_dim) with contiguous 16-byte-aligned
+    [T, rotary_dim/2] tables of one dtype, fp32 or bf16, on the device,
+    rotary_dim a multiple of 8 in (0, d]."""
+    if not (torch.is_tensor(qkv) and qkv.is_cuda
+            and qkv.dtype == torch.bfloat16 and qkv.dim() == 5
+            and qkv.shape[3] == 3 and qkv.stride(4) == 1
+            and qkv.stride(3) == qkv.shape[4] and _rows_aligned16(qkv)):
+        return False
+    B, S, h, _, D = qkv.shape
+    if D % 16 != 0 or not 16 <= D <= 256 or B * S * h >= 2 ** 31:
+        return False
+    if isinstance(cache_k, tuple) != isinstance(cache_v, tuple):
+        return False
+    if isinstance(cache_k, tuple):
+        (ck, ks), (cv, vs) = cache_k, cache_v
+        if not (_kv8_ok(ck, ks, qkv, 8) and _kv8_ok(cv, vs, qkv, 8)):
+            return False
+    else:
+        ck, cv = cache_k, cache_v
+        for t in (ck, cv):
+            if not (t.is_cuda and t.device == qkv.device
+                    and t.dtype == torch.bfloat16 and t.dim() == 4
+                    and t.stride(3) == 1 and _rows_aligned16(t)):
+                return False
+    if ck.shape != cv.shape or ck.shape[:2] != (B, h) or ck.shape[3] != D:
+        return False
+    if torch.is_tensor(pos) and not (
+            pos.device == qkv.device and pos.is_contiguous()
+            and pos.dtype in (torch.int32, torch.int64)
+            and pos.shape == (B,)):
+        return False
+    if rotary is not None:
+        sin, cos, rd = rotary
+        if rd % 8 != 0 or not 0 < rd <= D:
+            return False
+        for t in (sin, cos):
+            if not (t.is_cuda and t.device == qkv.device
+                    and t.dtype == sin.dtype
+                    and t.dtype in (torch.float32, torch.bfloat16)
+                    and t.dim() == 2 and t.shape == (sin.shape[0], rd // 2)
+                    and t.is_contiguous() and t.data_ptr() % 16 == 0):
+                return False
+    return use_hip(qkv)
+
+
+@torch.no_grad()
+def qkv_cache_write(qkv: torch.Tensor, cache_k, cache_v, pos, rotary=None,
+                    want_k: bool = False, _in_envelope: bool = False):
+    """Everything between the qkv projection and the attention kernel of a
+    cached decoder step: split the packed qkv [B, S, h, 3, d], rotate q and
+    k, and write k and v into the KV cache.  Returns q [B, h, S, d]
+    contiguous, or (q, k_new) with want_k (k_new the rotated k, same shape).
+    Inference only.
+
+    cache_k and cache_v are what KVCache.layer returns, views included: bf16
+    [B, h, L, d], or (bytes, scales) pairs of the e4m3 cache.  Row
+    (b, head, s) sits at position p = pos_b + s and goes to cache row p; pos
+    is an int or an int32/int64 [B] tensor, read on the device only, so the
+    call can be captured in a graph.  rotary is None or (sin, cos,
+    rotary_dim) with tables [T, rotary_dim/2], fp32 or bf16: GPT-J interleaved
+    pairs on the first rotary_dim columns, y0 = x0*c - x1*s and y1 = x0*s +
+    x1*c in fp32 with every operation rounded on its own, then rounded to
+    bf16 once.  The other columns and v are copied bit for bit; an e4m3 cache
+    row is what kv_cache_append_fp8 makes of the rounded row.  A row with p
+    outside [0, L), or outside the tables, is zero in q (and k_new) and
+    writes nothing to the cache; an int pos whose rows leave the tables is
+    refused.  Older cache rows are never touched.
+
+    Inside qkv_cache_write_ok this is one launch of the gfx950 kernel
+    (csrc/qkv_cache_write.hip), which reads qkv in place.  On CPU or outside
+    the envelope it is reference.qkv_cache_write.  (_in_envelope: the caller
+    has just had True from qkv_cache_write_ok for these operands, so the
+    Python-side check is not repeated; the binding checks them in any case.)"""
+    if not (_in_envelope or
+            qkv_cache_write_ok(qkv, cache_k, cache_v, pos, rotary)):
+        return ref.qkv_cache_write(qkv, cache_k, cache_v, pos, rotary, want_k)
+    if isinstance(cache_k, tuple):
+        (ck, ks), (cv, vs) = cache_k, cache_v
+    else:
+        ck, cv, ks, vs = cache_k, cache_v, None, None
+    sin, cos, rd = rotary if rotary is not None else (None, None, 0)
+    host, dev = (0, pos) if torch.is_tensor(pos) else (int(pos), None)
+    out = hip_ops().qkv_cache_write(qkv, ck, cv, ks, vs, host, dev, sin, cos,
+                                    rd, want_k)
+    return tuple(out) if want_k else out[0]
 
 
 @torch.no_grad()

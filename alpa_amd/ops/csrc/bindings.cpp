@@ -844,6 +844,101 @@ void kv_cache_append(const at::Tensor& k, const at::Tensor& v, at::Tensor k8,
       opt_ptr(pos_dev), pos_kind, strides.data(), cur_stream()));
 }
 
+// Split the packed qkv [B,S,H,3,D] bf16 view, rotate q and k, write q (and
+// k_new if want_k) [B,H,S,D] contiguous and write k, v at row pos_b + s of
+// the cache (qkv_cache_write.hip).  Cache: bf16 views [B,H,L,D] (k_scale and
+// v_scale absent) or the e4m3 cache with its scales.  pos_dev as in
+// kv_cache_append.  sin and cos: absent, or tables [T, rotary_dim/2] of one
+// dtype, fp32 or bf16.  Rows outside [0, L) or the tables are masked on the
+// device; a host position whose rows leave the tables is refused here.
+std::vector<at::Tensor> qkv_cache_write(
+    const at::Tensor& qkv, at::Tensor cache_k, at::Tensor cache_v,
+    const c10::optional<at::Tensor>& k_scale,
+    const c10::optional<at::Tensor>& v_scale, int64_t pos_host,
+    const c10::optional<at::Tensor>& pos_dev,
+    const c10::optional<at::Tensor>& sin, const c10::optional<at::Tensor>& cos,
+    int64_t rotary_dim, bool want_k) {
+  check_typed(qkv, "qkv", at::kBFloat16, qkv);
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(3) == 3,
+              "qkv must be 5-D [B,S,H,3,D]");
+  const int64_t B = qkv.size(0), S = qkv.size(1), H = qkv.size(2),
+                D = qkv.size(4);
+  TORCH_CHECK(D >= 16 && D % 16 == 0 && D <= 256,
+              "head_dim must be a multiple of 16 in [16, 256], got ", D);
+  TORCH_CHECK(qkv.stride(4) == 1, "qkv head-dim must be contiguous");
+  TORCH_CHECK(qkv.stride(3) == D, "qkv: the q, k and v rows of a head must "
+              "lie head_dim apart, got stride ", qkv.stride(3));
+  check_rows_aligned16(qkv, "qkv");
+  const bool fp8 = given(k_scale);
+  TORCH_CHECK(fp8 == given(v_scale),
+              "k_scale and v_scale must both be given or both absent");
+  int64_t L;
+  if (fp8) {
+    check_kv8(cache_k, *k_scale, "cache_k", "k_scale", B, H, -1, D, 8, qkv);
+    L = cache_k.size(2);
+    check_kv8(cache_v, *v_scale, "cache_v", "v_scale", B, H, L, D, 8, qkv);
+  } else {
+    check_bhsd(cache_k, "cache_k", B, H, -1, D, qkv);
+    L = cache_k.size(2);
+    check_bhsd(cache_v, "cache_v", B, H, L, D, qkv);
+    check_rows_aligned16(cache_k, "cache_k");
+    check_rows_aligned16(cache_v, "cache_v");
+  }
+  int pos_kind = 0;
+  if (given(pos_dev)) {
+    const bool i32 = pos_dev->scalar_type() == at::kInt;
+    TORCH_CHECK(i32 || pos_dev->scalar_type() == at::kLong,
+                "pos must be int32 or int64");
+    check_vec(*pos_dev, "pos", pos_dev->scalar_type(), B, qkv);
+    pos_kind = i32 ? 1 : 2;
+  }
+  int table_kind = 0;
+  int64_t T = 0;
+  TORCH_CHECK(given(sin) == given(cos),
+              "sin and cos must both be given or both absent");
+  if (given(sin)) {
+    TORCH_CHECK(rotary_dim > 0 && rotary_dim % 8 == 0 && rotary_dim <= D,
+                "rotary_dim must be a multiple of 8 in (0, head_dim], got ",
+                rotary_dim);
+    const at::ScalarType tt = sin->scalar_type();
+    TORCH_CHECK(tt == at::kFloat || tt == at::kBFloat16,
+                "sin and cos must be fp32 or bf16");
+    TORCH_CHECK(sin->dim() == 2 && sin->size(1) == rotary_dim / 2,
+                "sin must be [T, rotary_dim/2]");
+    T = sin->size(0);
+    check_vec(*sin, "sin", tt, T * (rotary_dim / 2), qkv);
+    check_vec(*cos, "cos", tt, T * (rotary_dim / 2), qkv);
+    TORCH_CHECK(cos->dim() == 2 && cos->size(0) == T, "cos must have the "
+                "shape of sin");
+    for (const at::Tensor* t : {&*sin, &*cos})
+      TORCH_CHECK(reinterpret_cast<uintptr_t>(t->const_data_ptr()) % 16 == 0,
+                  "sin and cos must be 16-byte aligned");
+    TORCH_CHECK(pos_kind != 0 || (pos_host >= 0 && pos_host + S <= T),
+                "positions ", pos_host, " .. ", pos_host + S - 1,
+                " are outside the rotary tables of ", T, " rows");
+    table_kind = tt == at::kFloat ? 1 : 2;
+  }
+  TORCH_CHECK(B * S * H <= INT32_MAX, "qkv: at most 2^31 - 1 (batch, seq, "
+              "head) triples, got ", B * S * H);
+  auto q = at::empty({B, H, S, D}, qkv.options());
+  std::vector<at::Tensor> out = {q};
+  if (want_k) out.push_back(at::empty({B, H, S, D}, qkv.options()));
+  std::array<int64_t, 15> strides = {qkv.stride(0), qkv.stride(1),
+                                     qkv.stride(2)};
+  const auto cache_st = fp8 ? bhs_strides(cache_k, cache_v, *k_scale, *v_scale)
+                            : bhs_strides(cache_k, cache_v, cache_k, cache_v);
+  std::copy(cache_st.begin(), cache_st.end(), strides.begin() + 3);
+  HIP_OK(launch_qkv_cache_write(
+      qkv.const_data_ptr(), q.mutable_data_ptr(),
+      want_k ? out[1].mutable_data_ptr() : nullptr, cache_k.mutable_data_ptr(),
+      cache_v.mutable_data_ptr(),
+      fp8 ? (float*)k_scale->mutable_data_ptr() : nullptr,
+      fp8 ? (float*)v_scale->mutable_data_ptr() : nullptr, fp8 ? 1 : 0,
+      opt_ptr(sin), opt_ptr(cos), table_kind, rotary_dim, T, B, S, H, D, L,
+      pos_host, opt_ptr(pos_dev), pos_kind, strides.data(), cur_stream()));
+  return out;
+}
+
 // attn_decode over the e4m3 cache (attention_decode_fp8.hip): q [B,H,1,D]
 // bf16, k8 and v8 [B,H,Skv,D] e4m3 views with 16-byte-aligned rows, k_scale
 // and v_scale [B,H,Skv] fp32 views.  Returns (o [B,H,1,D] bf16, lse [B,H,1]).
@@ -1393,7 +1488,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // 11: attn_chunk and attn_chunk_fp8 added (query chunks over a KV cache)
   // 12: AdamW descriptor rows are 8 words (twin, rows, cols added);
   // adamw_check_twin added
-  m.attr("ABI_VERSION") = 12;
+  // 13: qkv_cache_write added (fused qkv split, rotary and KV-cache write)
+  m.attr("ABI_VERSION") = 13;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)",
         py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),
@@ -1461,6 +1557,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k"), py::arg("v"), py::arg("k8"), py::arg("k_scale"),
         py::arg("v8"), py::arg("v_scale"), py::arg("pos"),
         py::arg("pos_dev") = py::none());
+  m.def("qkv_cache_write", &qkv_cache_write,
+        "qkv split + rotary + KV-cache write, bf16 or e4m3 cache (gfx950)",
+        py::arg("qkv"), py::arg("cache_k"), py::arg("cache_v"),
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
+        py::arg("pos") = 0, py::arg("pos_dev") = py::none(),
+        py::arg("sin") = py::none(), py::arg("cos") = py::none(),
+        py::arg("rotary_dim") = 0, py::arg("want_k") = false);
   m.def("attn_decode_fp8", &attn_decode_fp8,
         "split-KV decode attention over the e4m3 cache (gfx950)",
         py::arg("q"), py::arg("k8"), py::arg("k_scale"), py::arg("v8"),

@@ -26,18 +26,17 @@
 // is an integer max over the |x| bit patterns (NaN > Inf > every finite
 // value, so one reduction also finds a non-finite row), reduced by xor
 // shuffles inside the lane group.  One lane writes the scale, every live
-// lane its 8 bytes with one 8-byte store.  No LDS, no atomics.
+// lane its 8 bytes with one 8-byte store.  No LDS, no atomics.  The row
+// quantize itself is kv_row_quant.h, shared with qkv_cache_write.hip.
 //
 // Resource usage (gfx950, -Rpass-analysis=kernel-resource-usage) at every
 // Dp: 22 VGPRs, 8 waves per SIMD, no LDS, no scratch.
 #include <cstring>
 
-#include "fused_math.h"
+#include "kv_row_quant.h"
 #include "launchers.h"
 
 #define KVA_THREADS 256
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // (batch, head, seq) strides: sources in bf16 elements, caches in bytes,
 // scales in fp32 elements
@@ -85,32 +84,13 @@ __global__ __launch_bounds__(KVA_THREADS) void kv_cache_append_kernel(
     x = *reinterpret_cast<const bf16x8*>(src + dg);
   }
   float f[8];
-  unsigned int abits = 0u;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    f[j] = bf2f(x[j]);
-    abits = max(abits, __float_as_uint(f[j]) & 0x7fffffffu);
-  }
-#pragma unroll
-  for (int off = 1; off < LPR; off <<= 1)
-    abits = max(abits, (unsigned int)__shfl_xor((int)abits, off, 64));
+  for (int j = 0; j < 8; ++j) f[j] = bf2f(x[j]);
+  const unsigned int abits = kv_row_amax_bits<LPR>(f);
   if (!live) return;
 
-  const bool bad = abits >= 0x7f800000u;      // the row holds a NaN or an Inf
-  const float scale = bad          ? __uint_as_float(0x7fc00000u)
-                      : abits == 0u ? 1.0f
-                                    : __uint_as_float(abits) / 448.0f;
-  u32x2 bytes = {0x7f7f7f7fu, 0x7f7f7f7fu};
-  if (!bad) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const unsigned int lo =
-          cvt2_fp8<false>(f[4 * h] / scale, f[4 * h + 1] / scale);
-      const unsigned int hi =
-          cvt2_fp8<false>(f[4 * h + 2] / scale, f[4 * h + 3] / scale);
-      bytes[h] = lo | (hi << 16);
-    }
-  }
+  const float scale = kv_row_scale(abits);
+  const u32x2 bytes = kv_row_pack(f, abits, scale);
   unsigned char* dst =
       is_v ? v8 + batch * st.v8b + head * st.v8h + at * st.v8s
            : k8 + batch * st.k8b + head * st.k8h + at * st.k8s;

@@ -219,6 +219,24 @@ hipError_t launch_kv_cache_append(const void* k, const void* v, void* k8,
                                   const void* pos_dev, int pos_kind,
                                   const int64_t* strides, hipStream_t stream);
 
+// ---- qkv_cache_write.hip ----
+// split the packed qkv [B,S,H,3,D] bf16 (16-byte-aligned rows), rotate q and
+// k (table_kind 0: no rotary; 1 / 2: sin_t, cos_t [T, rotary_dim/2] fp32 /
+// bf16), write q_out and (unless null) k_new [B,H,S,D] contiguous, and write
+// k and v at row pos_b + s of the cache: cache_fp8 0, bf16 [B,H,L,D] with
+// 16-byte-aligned rows (scales null); 1, the e4m3 cache of kv_cache_fp8.hip.
+// A row whose position is outside [0, L), or outside the tables, is written
+// as zeros to q_out / k_new and not at all to the cache.  pos_kind as in
+// launch_kv_cache_append.  strides: qkv (batch, seq, head), cache_k(3),
+// cache_v(3), k_scale(3), v_scale(3)
+hipError_t launch_qkv_cache_write(
+    const void* qkv, void* q_out, void* k_new, void* cache_k, void* cache_v,
+    float* k_scale, float* v_scale, int cache_fp8, const void* sin_t,
+    const void* cos_t, int table_kind, int64_t rotary_dim, int64_t T,
+    int64_t B, int64_t S, int64_t H, int64_t D, int64_t L, int64_t pos_host,
+    const void* pos_dev, int pos_kind, const int64_t* strides,
+    hipStream_t stream);
+
 // ---- moe_route.hip ----
 // top-2 + in-block ranks (left in slot1/slot2) + per-256-token-block
 // histograms and softmax column partials, all [ceil(N/256), E]

@@ -230,6 +230,63 @@ def kv_cache_append_fp8(k, v, k8, k_scale, v8, v_scale, pos) -> None:
         cs[b_idx, :, at] = sc[b_idx, :, s_idx]
 
 
+def qkv_cache_write(qkv, cache_k, cache_v, pos, rotary=None, want_k=False):
+    """The specification of csrc/qkv_cache_write.hip.  qkv [B, S, h, 3, d]
+    (any float dtype); cache_k, cache_v tensors [B, h, L, d] or the (bytes,
+    scales) pairs of the e4m3 cache; pos an int or an int tensor [B]; rotary
+    None or (sin, cos, rotary_dim) with tables [T, rotary_dim/2].  Row
+    (b, head, s) sits at p = pos_b + s.  q and k are rotated (GPT-J
+    interleaved pairs, the first rotary_dim columns) in fp32, every multiply,
+    add and subtract rounded on its own, and rounded to qkv's dtype; k and v
+    go to cache row p (an e4m3 cache through kv_cache_append_fp8 of the
+    rounded rows).  A row with p outside [0, L), or outside the tables, is
+    zero in q (and k_new) and writes nothing.  Returns q [B, h, S, d]
+    contiguous, or (q, k_new) with want_k."""
+    B, S, h, _, d = qkv.shape
+    dev = qkv.device
+    fp8 = isinstance(cache_k, tuple)
+    L = (cache_k[0] if fp8 else cache_k).shape[2]
+    if torch.is_tensor(pos):
+        p0 = pos.to(dev).long()
+    else:
+        p0 = torch.full((B,), int(pos), dtype=torch.long, device=dev)
+    at = p0.view(B, 1) + torch.arange(S, device=dev).view(1, S)
+    q, k, v = (qkv[:, :, :, i].permute(0, 2, 1, 3) for i in range(3))
+    if rotary is not None:
+        sin, cos, rd = rotary
+        T = sin.shape[0]
+        if not torch.is_tensor(pos) and not 0 <= int(pos) <= T - S:
+            raise ValueError(f"positions {pos} .. {int(pos) + S - 1} are "
+                             f"outside the rotary tables of {T} rows")
+        L = min(L, T)
+        row = at.clamp(0, max(T - 1, 0))
+        sn = sin.to(dev).float()[row].view(B, 1, S, rd // 2)
+        cs = cos.to(dev).float()[row].view(B, 1, S, rd // 2)
+
+        def rot(x):
+            pairs = x[..., :rd].float().reshape(B, h, S, rd // 2, 2)
+            x0, x1 = pairs[..., 0], pairs[..., 1]
+            y = torch.stack([x0 * cs - x1 * sn, x0 * sn + x1 * cs], dim=-1)
+            return torch.cat([y.flatten(-2).to(x.dtype), x[..., rd:]], dim=-1)
+
+        q, k = rot(q), rot(k)
+    valid = (at >= 0) & (at < L)
+    keep = valid.view(B, 1, S, 1)
+    q_out = torch.where(keep, q, torch.zeros_like(q)).contiguous()
+    k_new = torch.where(keep, k, torch.zeros_like(k)).contiguous()
+    # rows at or past min(L, T) are skipped: write through views that end there
+    if fp8:
+        (k8, ks), (v8, vs) = cache_k, cache_v
+        kv_cache_append_fp8(k, v, k8[:, :, :L], ks[:, :, :L], v8[:, :, :L],
+                            vs[:, :, :L], p0)
+    else:
+        b_idx, s_idx = torch.nonzero(valid, as_tuple=True)
+        rows = at[b_idx, s_idx]
+        cache_k[b_idx, :, rows] = k[b_idx, :, s_idx].to(cache_k.dtype)
+        cache_v[b_idx, :, rows] = v[b_idx, :, s_idx].to(cache_v.dtype)
+    return (q_out, k_new) if want_k else q_out
+
+
 def attention_decode_fp8(q, k8, k_scale, v8, v_scale, softmax_scale=None,
                          alibi=None, kv_lens=None):
     """attention_fwd (non-causal) over the dequantized cache; rows at or

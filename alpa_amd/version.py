@@ -16,8 +16,9 @@ __version__ = "0.1.0"
 #: every autograd function passes; 10: kv_cache_append and attn_decode_fp8,
 #: the e4m3 KV cache; 11: attn_chunk and attn_chunk_fp8, query chunks over a
 #: KV cache; 12: 8-word AdamW descriptor rows with the twin fields, and
-#: adamw_check_twin)
-MIN_HIP_OPS_ABI = 12
+#: adamw_check_twin; 13: qkv_cache_write, the fused qkv split, rotary and
+#: KV-cache write)
+MIN_HIP_OPS_ABI = 13
 
 
 def check_hip_ops_version() -> int:

@@ -47,7 +47,8 @@ def main():
                         "read per token — decode is weight-bandwidth-"
                         "bound, so this is the serving fp8 lever")
     p.add_argument("--graph", action="store_true",
-                   help="hipGraph-captured decode step (OPT only): one "
+                   help="hipGraph-captured decode step (CodeGen needs "
+                        "global_config.fused_qkv_write on): one "
                         "graph replay per token instead of ~15 eager op "
                         "dispatches per layer")
     p.add_argument("--check", action="store_true",
