@@ -162,6 +162,33 @@ class GlobalConfig:
     fused_qkv_write: str = field(
         default_factory=lambda: os.environ.get("ALPA_AMD_FUSED_QKV", "1"))
 
+    #: the pass over the vocabulary that picks a decode step's next token
+    #: as two kernels (ops/csrc/logits_sample.hip): ops.logits_topk gives
+    #: GenerationMixin._log_probs_topk (sampling, every beam_search step)
+    #: the local max, sum-exp and top-k in one read of the logits, and
+    #: ops.sample_logits is sample_token at tp == 1, with temperature,
+    #: top-k and top-p read per row on the device, which is what lets
+    #: generate_graphed and ContinuousBatcher sample.  A GPU draw is the
+    #: inverse CDF at one uniform per row, not torch.multinomial: a seed
+    #: gives other tokens than with the switch off.
+    #: Rule: every call inside ops.logits_topk_ok takes the kernels,
+    #: because no shape class measured slower than the torch ops
+    #: (tools/sampling_bench.py on one MI355X, table in docs/BENCHMARK.md,
+    #: "Fused sampling"; bf16 logits, V 50272 / 51200 / 250880, batch 1-64,
+    #: k 4 / 64; us per host-dispatched call, torch -> fused, spread <=
+    #: 0.21).  sample_token: 207-254 -> 43-46 at V ~ 50k (4.7-5.8x),
+    #: 249-492 -> 48-82 at V 250880 (5.0-7.4x).  _log_probs_topk: 89-168 ->
+    #: 39-42 (2.3-4.0x) and 155-406 -> 40-77 (3.2-8.2x).  The fused figures
+    #: at V ~ 50k are the host's dispatch floor, not device time.  The
+    #: segment width was fixed from the register budget, not swept.
+    #: Inside a captured graph and end to end (serve_bench) nothing was
+    #: measured.
+    #: "1" (default) on; ALPA_AMD_FUSED_SAMPLING=0 restores the torch ops
+    #: (and with them greedy-only graphs and batches).
+    fused_sampling: str = field(
+        default_factory=lambda: os.environ.get("ALPA_AMD_FUSED_SAMPLING",
+                                               "1"))
+
     #: bf16 dX GEMMs of the parallel linear layers read a transposed copy
     #: of the weight (its "twin", ops.weight_twin) that the fused AdamW
     #: kernel writes next to the weight: dY @ W (NN) becomes the TN GEMM

@@ -22,7 +22,7 @@ from .. import ops
 from ..mesh import DeviceMesh
 from ..parallel.layers import (ColumnParallelLinear, RowParallelLinear,
                                VocabParallelEmbedding)
-from .generation import GenerationMixin
+from .generation import GenerationMixin, draw_uniforms, fused_sampling_on
 from .gpt import LayerNorm
 
 
@@ -366,16 +366,30 @@ class CachedDecoder(nn.Module, GenerationMixin):
 
     @torch.no_grad()
     def graphed_decoder(self, prompt_ids: torch.Tensor,
-                        max_new_tokens: int) -> "_GraphedDecode":
+                        max_new_tokens: int, do_sample: bool = False,
+                        temperature: float = 1.0, top_k: int = 0,
+                        top_p: float = 1.0,
+                        generator: Optional[torch.Generator] = None
+                        ) -> "_GraphedDecode":
         """Prefill + capture now; `.run()` replays the decode loop
         (single use — the cache advances).  Lets benchmarks time the
         replay loop separately from the one-time capture."""
-        return _GraphedDecode(self, prompt_ids, max_new_tokens)
+        return _GraphedDecode(self, prompt_ids, max_new_tokens, do_sample,
+                              temperature, top_k, top_p, generator)
 
     @torch.no_grad()
     def generate_graphed(self, prompt_ids: torch.Tensor,
-                         max_new_tokens: int) -> torch.Tensor:
-        """Greedy generate with the DECODE STEP hipGraph-captured.
+                         max_new_tokens: int, do_sample: bool = False,
+                         temperature: float = 1.0, top_k: int = 0,
+                         top_p: float = 1.0,
+                         generator: Optional[torch.Generator] = None
+                         ) -> torch.Tensor:
+        """Greedy (default) or sampled generate with the DECODE STEP
+        hipGraph-captured.  With do_sample the step ends in
+        ops.sample_logits (global_config.fused_sampling must be on): the
+        uniforms of all steps are drawn before capture and the captured
+        step takes its row by a device step counter, so the result equals
+        generate(do_sample=True) with an equally seeded generator.
 
         Eager decode is host-bound (~23 us/op measured: OPT-66B 28.1
         ms/token = ~1200 op dispatches) — capturing one whole decode
@@ -386,35 +400,58 @@ class CachedDecoder(nn.Module, GenerationMixin):
         lens, the cache scatter and wpe gather index by lens, and the
         cache view is a fixed capacity (prompt + max_new_tokens).
         Single-mesh (tp=1) path; requires CUDA."""
-        return self.graphed_decoder(prompt_ids, max_new_tokens).run()
+        return self.graphed_decoder(prompt_ids, max_new_tokens, do_sample,
+                                    temperature, top_k, top_p,
+                                    generator).run()
 
 
 class _GraphedDecode:
     """See CachedDecoder.generate_graphed."""
 
     @torch.no_grad()
-    def __init__(self, model, prompt_ids, max_new_tokens):
+    def __init__(self, model, prompt_ids, max_new_tokens, do_sample=False,
+                 temperature=1.0, top_k=0, top_p=1.0, generator=None):
         assert prompt_ids.is_cuda and (
             model.mesh is None or model.mesh.axis_size(model.axis) == 1)
         B, S0 = prompt_ids.shape
+        dev = prompt_ids.device
         self.model, self.prompt_ids = model, prompt_ids
         self.max_new = max_new_tokens
         cap = S0 + max_new_tokens
         cache = model.new_cache(B, max_len=cap)
         logits = model.forward_step(prompt_ids, cache)
-        tok = self.tok = model.greedy_token(logits).reshape(B, 1).clone()
+        if do_sample:
+            # the multinomial draw of the torch path reads the generator on
+            # the host: only the kernel's draw can be captured
+            assert fused_sampling_on(), \
+                "a sampled graph needs global_config.fused_sampling"
+            us = draw_uniforms(max_new_tokens, B, generator, dev)
+            # row of `us` the next step consumes, advanced inside the graph
+            nstep = torch.ones(1, dtype=torch.long, device=dev)
+
+            def pick(lg, u):
+                return model.sample_token(lg, temperature, top_k, top_p,
+                                          u=u)
+
+            tok = pick(logits, us[0])
+        else:
+            tok = model.greedy_token(logits)
+        tok = self.tok = tok.reshape(B, 1).clone()
         lens = self.lens = torch.full((B,), S0, dtype=torch.long,
-                                      device=prompt_ids.device)
+                                      device=dev)
         out = self.out = torch.empty(B, max_new_tokens,
-                                     dtype=prompt_ids.dtype,
-                                     device=prompt_ids.device)
+                                     dtype=prompt_ids.dtype, device=dev)
         out[:, 0] = tok[:, 0]
 
         def step():
             lg = model.forward_decode(tok, cache, lens, cap=cap)
-            nxt = model.greedy_token(lg).reshape(B, 1)
+            if do_sample:
+                nxt = pick(lg, us.index_select(0, nstep)[0])
+                nstep.add_(1)
+            else:
+                nxt = model.greedy_token(lg)
             lens.add_(1)
-            tok.copy_(nxt)
+            tok.copy_(nxt.reshape(B, 1))
 
         # warmup on a side stream (standard capture recipe), then capture
         side = torch.cuda.Stream()
@@ -425,6 +462,8 @@ class _GraphedDecode:
         # roll back the warmup step's state mutations
         lens.fill_(S0)
         tok[:, 0] = out[:, 0]
+        if do_sample:
+            nstep.fill_(1)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             step()

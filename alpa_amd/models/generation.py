@@ -21,7 +21,32 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
+from .. import ops
 from ..mesh import is_distributed
+
+
+def _fused_sampling_routed(logits: torch.Tensor, k: int) -> bool:
+    """Do _log_probs_topk and sample_token take the top-k and sampling
+    kernels for these logits?  The switch, its rule and the measurements
+    behind it are on global_config.fused_sampling."""
+    return fused_sampling_on() and \
+        ops.logits_topk_ok(logits, min(k, logits.shape[-1]))
+
+
+def fused_sampling_on() -> bool:
+    from ..global_env import global_config
+    return global_config.fused_sampling not in ("0", False)
+
+
+def draw_uniforms(steps: int, batch: int,
+                  generator: Optional[torch.Generator],
+                  device) -> torch.Tensor:
+    """All the uniforms of a sampled generation, [steps, batch] fp32 in
+    [0, 1) on `device`, in one draw on the generator's own device: the
+    eager and the graph-captured decode loop consume row i at step i."""
+    gdev = generator.device if generator is not None else device
+    return torch.rand(steps, batch, generator=generator,
+                      device=gdev).to(device)
 
 
 class GenerationMixin:
@@ -48,19 +73,37 @@ class GenerationMixin:
                                           device=best.device), 1]
         return idx.long()
 
+    def _tp(self) -> int:
+        return self.mesh.axis_size(self.axis) if self.mesh is not None else 1
+
     @torch.no_grad()
     def sample_token(self, logits: torch.Tensor, temperature: float = 1.0,
                      top_k: int = 0, top_p: float = 1.0,
-                     generator: Optional[torch.Generator] = None
-                     ) -> torch.Tensor:
+                     generator: Optional[torch.Generator] = None,
+                     u: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Temperature / top-k / top-p sampling, vocab-parallel-safe: the
         candidate set is the global top-max(top_k, 64) (covering all mass
         that survives top-p in practice); every TP rank draws the SAME
         sample (shared generator seed), so SPMD decode stays in lockstep.
+
+        On the GPU at tp == 1 (global_config.fused_sampling, inside
+        ops.logits_topk_ok) this is ops.sample_logits: one uniform per row
+        (`u` [B], else drawn from `generator`) through the inverse CDF of
+        the kept candidates, so a seed's draw differs from the multinomial
+        draw of the torch path below, which ignores `u`.
         """
         kk = max(top_k if top_k > 0 else 0, 64)
-        lp, idx = self._log_probs_topk(logits.float() / max(temperature,
-                                                            1e-6), kk)
+        inv_t = 1.0 / max(temperature, 1e-6)
+        if self._tp() == 1 and _fused_sampling_routed(logits, kk):
+            if u is None:
+                u = draw_uniforms(1, logits.shape[0], generator,
+                                  logits.device)[0]
+            return ops.sample_logits(logits, u, inv_t, top_k, top_p, k=kk)
+        if _fused_sampling_routed(logits, kk):
+            lp, idx = self._log_probs_topk(logits, kk, inv_t)
+        else:
+            lp, idx = self._log_probs_topk(logits.float() / max(temperature,
+                                                                1e-6), kk)
         if top_k > 0:
             lp = lp[:, :top_k]
             idx = idx[:, :top_k]
@@ -75,13 +118,23 @@ class GenerationMixin:
         return idx.gather(1, choice)[:, 0]
 
     @torch.no_grad()
-    def _log_probs_topk(self, logits: torch.Tensor, k: int):
+    def _log_probs_topk(self, logits: torch.Tensor, k: int,
+                        inv_temperature: float = 1.0):
         """Global top-k log-probs over the vocab-parallel logits without
         gathering the full vocab: the softmax normalizer comes from two
         scalar-per-row all-reduces (max, sumexp); candidates are local
         top-k + a tp-wide gather of (value, global index) pairs.  Every
-        rank computes identical results (SPMD-safe)."""
+        rank computes identical results (SPMD-safe).
+
+        On the GPU (global_config.fused_sampling, inside
+        ops.logits_topk_ok) the local max, sum-exp and top-k of logits *
+        inv_temperature come from ops.logits_topk in one read of the row,
+        and the collectives run on its [B]- and [B, k]-sized results.  The
+        torch path below takes logits already divided by the temperature.
+        """
         tp = self.mesh.axis_size(self.axis) if self.mesh is not None else 1
+        if _fused_sampling_routed(logits, k):
+            return self._log_probs_topk_fused(logits, k, inv_temperature)
         lf = logits.float()
         m = lf.max(dim=-1, keepdim=True).values
         if tp > 1 and is_distributed():
@@ -108,6 +161,36 @@ class GenerationMixin:
             vals, sel = vals.topk(min(k, vals.shape[-1]), dim=-1)
             idx = idx.gather(1, sel).long()
         return vals - log_z, idx
+
+    @torch.no_grad()
+    def _log_probs_topk_fused(self, logits: torch.Tensor, k: int,
+                              inv_temperature: float):
+        """_log_probs_topk from ops.logits_topk's per-rank (vals, idx, m,
+        s): the same collectives, on [B] and [B, k] tensors."""
+        tp = self._tp() if is_distributed() else 1
+        vocab_start = 0 if tp == 1 else \
+            self.mesh.axis_index(self.axis) * self.lm_head.out_per_rank
+        vals, idx, m, s = ops.logits_topk(logits, k, inv_temperature,
+                                          vocab_start)
+        if tp > 1:
+            group = self.mesh.axis_group(self.axis)
+            gm = m.clone()
+            dist.all_reduce(gm, op=dist.ReduceOp.MAX, group=group)
+            # s = 0 where m = -inf, but exp(-inf - -inf) is NaN
+            s = torch.where(m == gm, s, s * (m - gm).exp())
+            dist.all_reduce(s, group=group)
+            m = gm
+            kk = vals.shape[1]
+            pair = torch.cat([vals, idx.float()], dim=-1).contiguous()
+            gathered = torch.empty(tp * pair.shape[0], pair.shape[1],
+                                   dtype=pair.dtype, device=pair.device)
+            dist.all_gather_into_tensor(gathered, pair, group=group)
+            gathered = gathered.view(tp, -1, 2 * kk)
+            vals = gathered[:, :, :kk].permute(1, 0, 2).reshape(-1, tp * kk)
+            idx = gathered[:, :, kk:].permute(1, 0, 2).reshape(-1, tp * kk)
+            vals, sel = vals.topk(min(k, vals.shape[-1]), dim=-1)
+            idx = idx.gather(1, sel).long()
+        return vals - (m + s.log()).unsqueeze(-1), idx
 
     @torch.no_grad()
     def beam_search(self, prompt_ids: torch.Tensor, max_new_tokens: int,
@@ -174,21 +257,30 @@ class GenerationMixin:
                  ) -> torch.Tensor:
         """Greedy (default) or sampled generation: prefill + cached decode
         loop.  prompt_ids [B, S0]; returns [B, S0 + max_new_tokens].
-        With do_sample, pass the SAME generator seed on every TP rank."""
+        With do_sample, pass the SAME generator seed on every TP rank.
+        On the GPU at tp == 1 the uniforms of all steps are drawn up front
+        (draw_uniforms), as generate_graphed draws them, so the two return
+        the same tokens for equally seeded generators."""
         B, S0 = prompt_ids.shape
         cache = self.new_cache(B)
+        us = None
+        if do_sample and prompt_ids.is_cuda and self._tp() == 1 and \
+                fused_sampling_on():
+            us = draw_uniforms(max_new_tokens, B, generator,
+                               prompt_ids.device)
 
-        def pick(lg):
+        def pick(lg, step):
             if do_sample:
                 return self.sample_token(lg, temperature, top_k, top_p,
-                                         generator)
+                                         generator,
+                                         None if us is None else us[step])
             return self.greedy_token(lg)
 
         logits = self.forward_step(prompt_ids, cache)
-        toks = [pick(logits)]
-        for _ in range(max_new_tokens - 1):
+        toks = [pick(logits, 0)]
+        for step in range(1, max_new_tokens):
             logits = self.forward_step(toks[-1].unsqueeze(1), cache)
-            toks.append(pick(logits))
+            toks.append(pick(logits, step))
             if eos_token is not None and bool((toks[-1] == eos_token).all()):
                 break
         return torch.cat([prompt_ids] + [t.unsqueeze(1) for t in toks],

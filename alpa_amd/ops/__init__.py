@@ -32,7 +32,12 @@ under global_config.weight_fp4, MXFP4 weights: mxfp4_quantize and
 mxfp4_dequantize are that format (e2m1 codes, one e8m0 scale per 32 k),
 mxfp4_pack the layout its two kernels read.  weight_twin and its helpers
 keep the transposed copies of linear weights that fused_adamw writes and
-linear_bias's dX GEMM reads.
+linear_bias's dX GEMM reads.  logits_topk and sample_logits are the pass over
+the vocabulary that ends a decode step (top-k with the softmax max and
+sum-exp in one read of the row; temperature / top-k / top-p sampling with
+per-row parameters read on the device), which global_config.fused_sampling
+turns on in generation, beam search and the batcher; logits_topk_ok is
+their envelope.
 
 Kernel-level contract mirrors the reference's compiled-HLO op inventory
 (GEMM+epilogue, attention, LayerNorm, fused Adam,
@@ -61,7 +66,9 @@ __all__ = [
     "chunk_attn_fp8_ok",
     "softmax_cross_entropy",
     "softmax_cross_entropy_partial", "softmax_cross_entropy_combine",
-    "softmax_cross_entropy_shard_bwd", "vocab_ce_fused_ok", "fused_adamw",
+    "softmax_cross_entropy_shard_bwd", "vocab_ce_fused_ok",
+    "logits_topk", "logits_topk_ok", "sample_logits", "LOGITS_TOPK_SEG",
+    "fused_adamw",
     "multi_tensor_sumsq", "weight_twin", "weight_twin_eligible",
     "register_weight_twin", "weight_twin_written", "valid_weight_twin",
     "invalidate_weight_twin",
@@ -986,6 +993,93 @@ def softmax_cross_entropy_shard_bwd(dloss: torch.Tensor,
             lse, int(vocab_start))
     return ref.softmax_cross_entropy_shard_bwd(dloss, logits, targets, lse,
                                                int(vocab_start))
+
+
+# Columns per segment of the top-k kernels' partial pass: LS_BLOCK *
+# LS_ROUNDS 16-byte groups in csrc/logits_sample.hip (the extension's
+# logits_topk_segment reports them).  A function of the dtype alone.
+LOGITS_TOPK_SEG = {torch.bfloat16: 8192, torch.float32: 4096}
+
+
+def logits_topk_ok(logits: torch.Tensor, k: int) -> bool:
+    """Envelope of the top-k log-prob and sampling kernels
+    (csrc/logits_sample.hip; the bindings check the same): a 2-D bf16 or
+    fp32 tensor on the GPU with 1..65535 rows, contiguous columns and every
+    row 16-byte aligned (aligned base, row stride a multiple of 16 bytes: a
+    column slice or a row-strided view is fine), and 1 <= k <= min(V, 128)."""
+    if not (logits.is_cuda and logits.dim() == 2 and
+            logits.dtype in LOGITS_TOPK_SEG):
+        return False
+    B, V = logits.shape
+    if not (1 <= B <= 65535 and 1 <= k <= min(V, 128) and
+            V <= 2 ** 31 - 8193 and logits.stride(1) == 1):
+        return False
+    per16 = 16 // logits.element_size()
+    if logits.data_ptr() % 16 != 0 or (
+            B > 1 and (logits.stride(0) < 0 or logits.stride(0) % per16)):
+        return False
+    return use_hip(logits)
+
+
+def _row_param(value, B: int, dtype, device) -> torch.Tensor:
+    """A per-row kernel parameter as a contiguous [B] device tensor."""
+    if isinstance(value, torch.Tensor):
+        return value.to(device=device, dtype=dtype).reshape(-1).expand(
+            B).contiguous()
+    return torch.full((B,), value, dtype=dtype, device=device)
+
+
+@torch.no_grad()
+def logits_topk(logits: torch.Tensor, k: int, inv_temperature=None,
+                vocab_start: int = 0):
+    """Top-k of a row of logits with its softmax statistics, in one read:
+    logits [B, V], y = float(logits) * inv_temperature (a [B] tensor or a
+    number, default 1; one fp32 multiply) -> (vals [B, k] fp32 = the k
+    largest y, descending, equal y by lower column; idx [B, k] int64 =
+    column + vocab_start; m [B] = max y; s [B] = sum exp(y - m)).  The
+    log-probability of candidate j is vals[:, j] - m - log(s); over a vocab
+    shard, (m, s) and the candidates combine across shards as the
+    cross-entropy statistics do.  k is clamped to V.  A row of -inf only
+    gives m = -inf, s = 0; a NaN makes m and s NaN and leaves idx in range.
+    Inside logits_topk_ok this is the two gfx950 kernels (per-segment radix
+    select, fixed-order merge): a row's output bits depend on that row
+    alone, nothing is read back, so the call can be captured in a graph.
+    On CPU or outside the envelope it is reference.logits_topk."""
+    B, V = logits.shape
+    k = min(int(k), V)
+    if logits_topk_ok(logits, k):
+        inv_t = _row_param(1.0 if inv_temperature is None else
+                           inv_temperature, B, torch.float32, logits.device)
+        return tuple(hip_ops().logits_topk(logits, k, inv_t,
+                                           int(vocab_start)))
+    inv_t = None if inv_temperature is None else _row_param(
+        inv_temperature, B, torch.float32, logits.device)
+    return ref.logits_topk(logits, k, inv_t, int(vocab_start))
+
+
+@torch.no_grad()
+def sample_logits(logits: torch.Tensor, u: torch.Tensor, inv_temperature,
+                  top_k, top_p, k: int = 64) -> torch.Tensor:
+    """One token [B] int64 per row of logits [B, V] by temperature / top-k /
+    top-p sampling, every parameter per row ([B] tensors, or numbers shared
+    by the rows): u uniform in [0, 1), inv_temperature > 0, top_k (0 or
+    above k: all k candidates), top_p.  The candidates are logits_topk's k
+    (clamped to V) with p_j = exp(y_j - y_0); the smallest prefix reaching
+    top_p of their mass is kept (always candidate 0) and renormalised, and
+    the token is the inverse CDF of the kept prefix at u.  top_k = 1 is the
+    argmax with the lower column on a tie.  Inside logits_topk_ok the draw
+    happens in the merge kernel's launch, with no read-back; on CPU or
+    outside the envelope it is reference.sample_logits."""
+    B, V = logits.shape
+    k = min(int(k), V)
+    dev = logits.device
+    u = _row_param(u, B, torch.float32, dev)
+    inv_t = _row_param(inv_temperature, B, torch.float32, dev)
+    top_k = _row_param(top_k, B, torch.int32, dev)
+    top_p = _row_param(top_p, B, torch.float32, dev)
+    if logits_topk_ok(logits, k):
+        return hip_ops().logits_topk(logits, k, inv_t, 0, u, top_k, top_p)[4]
+    return ref.sample_logits(logits, u, inv_t, top_k, top_p, k)
 
 
 _ADAM_CHUNK = 16384  # must match ADAM_CHUNK in csrc/adamw.hip

@@ -38,7 +38,8 @@ EXTRA_FLAGS = {"skinny_mfma.hip": NO_PK_F32,
                "attention_chunk.hip": NO_PK_F32,
                "attention_decode_fp8.hip": NO_PK_F32,
                "kv_cache_fp8.hip": NO_PK_F32,
-               "qkv_cache_write.hip": NO_PK_F32}
+               "qkv_cache_write.hip": NO_PK_F32,
+               "logits_sample.hip": NO_PK_F32}
 
 
 def _torch_paths():

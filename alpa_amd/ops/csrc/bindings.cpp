@@ -652,6 +652,81 @@ at::Tensor cross_entropy_shard_bwd(const at::Tensor& dloss,
   return dlogits;
 }
 
+// optional operand: is it there, and its data pointer or nullptr
+bool given(const c10::optional<at::Tensor>& t) {
+  return t.has_value() && t->defined();
+}
+
+const void* opt_ptr(const c10::optional<at::Tensor>& t) {
+  return given(t) ? t->const_data_ptr() : nullptr;
+}
+
+// ---------------------- top-k log-probs and sampling ----------------------
+
+// logits [B, V] bf16 or fp32 with a contiguous last dimension and 16-byte-
+// aligned rows (any row stride that keeps them aligned), 1 <= k <= min(V,
+// 128), inv_temperature fp32 [B].  Returns (vals [B, k] fp32, idx [B, k]
+// int64, m [B], s [B]) and, when u, top_p (fp32 [B]) and top_k (int32 [B])
+// are given, all three, the drawn token [B] int64 as a fifth tensor.
+std::vector<at::Tensor> logits_topk(
+    const at::Tensor& logits, int64_t k, const at::Tensor& inv_temperature,
+    int64_t vocab_start, const c10::optional<at::Tensor>& u,
+    const c10::optional<at::Tensor>& top_k,
+    const c10::optional<at::Tensor>& top_p) {
+  check_device(logits, "logits", logits);
+  const bool bf16 = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf16 || logits.scalar_type() == at::kFloat,
+              "logits must be bf16 or fp32");
+  TORCH_CHECK(logits.dim() == 2, "logits must be 2-D");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535, "logits must have 1..65535 rows, got ",
+              B);
+  TORCH_CHECK(V >= 1 && V <= INT32_MAX - 8192,
+              "logits must have 1..2^31 - 8193 columns, got ", V);
+  TORCH_CHECK(logits.stride(1) == 1, "logits columns must be contiguous");
+  const int64_t per16 = bf16 ? 8 : 4;
+  TORCH_CHECK(
+      reinterpret_cast<uintptr_t>(logits.const_data_ptr()) % 16 == 0 &&
+          (B == 1 || (logits.stride(0) >= 0 && logits.stride(0) % per16 == 0)),
+      "logits rows must be 16-byte aligned");
+  TORCH_CHECK(k >= 1 && k <= 128 && k <= V,
+              "k must be in 1..min(V, 128), got ", k);
+  TORCH_CHECK(vocab_start >= 0, "vocab_start must be >= 0");
+  check_vec(inv_temperature, "inv_temperature", at::kFloat, B, logits);
+  const bool draw = given(u);
+  TORCH_CHECK(draw == given(top_k) && draw == given(top_p),
+              "u, top_k and top_p must be given together");
+  if (draw) {
+    check_vec(*u, "u", at::kFloat, B, logits);
+    check_vec(*top_k, "top_k", at::kInt, B, logits);
+    check_vec(*top_p, "top_p", at::kFloat, B, logits);
+  }
+  const int64_t nseg = (V + logits_topk_segment(bf16) - 1) /
+                       logits_topk_segment(bf16);
+  const auto f32 = logits.options().dtype(at::kFloat);
+  auto stats = at::empty({B, nseg, 2}, f32);
+  auto cand_val = at::empty({B, nseg, k}, f32);
+  auto cand_col = at::empty({B, nseg, k}, f32.dtype(at::kInt));
+  auto vals = at::empty({B, k}, f32);
+  auto idx = at::empty({B, k}, f32.dtype(at::kLong));
+  auto m = at::empty({B}, f32);
+  auto s = at::empty({B}, f32);
+  at::Tensor token;
+  if (draw) token = at::empty({B}, f32.dtype(at::kLong));
+  HIP_OK(launch_logits_topk(
+      logits.const_data_ptr(), bf16, B == 1 ? V : logits.stride(0),
+      (const float*)inv_temperature.const_data_ptr(), B, V, (int)k,
+      vocab_start, (float*)stats.mutable_data_ptr(),
+      (float*)cand_val.mutable_data_ptr(), (int*)cand_col.mutable_data_ptr(),
+      (float*)vals.mutable_data_ptr(), (int64_t*)idx.mutable_data_ptr(),
+      (float*)m.mutable_data_ptr(), (float*)s.mutable_data_ptr(),
+      (const float*)opt_ptr(u), (const int*)opt_ptr(top_k),
+      (const float*)opt_ptr(top_p),
+      draw ? (int64_t*)token.mutable_data_ptr() : nullptr, cur_stream()));
+  if (draw) return {vals, idx, m, s, token};
+  return {vals, idx, m, s};
+}
+
 // ------------------------------ Attention --------------------------------
 
 // q/k/v/o are logical [B, H, S, D] views with arbitrary B/H/S strides and a
@@ -666,15 +741,6 @@ std::array<int64_t, 3 * sizeof...(T)> bhs_strides(const T&... t) {
   int64_t* p = s.data();
   ((*p++ = t.stride(0), *p++ = t.stride(1), *p++ = t.stride(2)), ...);
   return s;
-}
-
-// optional operand: is it there, and its data pointer or nullptr
-bool given(const c10::optional<at::Tensor>& t) {
-  return t.has_value() && t->defined();
-}
-
-const void* opt_ptr(const c10::optional<at::Tensor>& t) {
-  return given(t) ? t->const_data_ptr() : nullptr;
 }
 
 // The inputs every fused attention entry takes: q [B,H,S,D]; k and v
@@ -1489,7 +1555,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // 12: AdamW descriptor rows are 8 words (twin, rows, cols added);
   // adamw_check_twin added
   // 13: qkv_cache_write added (fused qkv split, rotary and KV-cache write)
-  m.attr("ABI_VERSION") = 13;
+  // 14: logits_topk and logits_topk_segment added (top-k log-prob statistics
+  // and top-k / top-p sampling)
+  m.attr("ABI_VERSION") = 14;
   m.def("layer_norm_fwd", &layer_norm_fwd, "LayerNorm forward (gfx950)");
   m.def("layer_norm_bwd", &layer_norm_bwd, "LayerNorm backward (gfx950)",
         py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),
@@ -1537,6 +1605,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "vocab-shard CE partial stats [3, N] (gfx950)");
   m.def("cross_entropy_shard_bwd", &cross_entropy_shard_bwd,
         "vocab-shard CE bwd (gfx950)");
+  m.def("logits_topk", &logits_topk,
+        "top-k of y = logits * inv_temperature with max and sum-exp, and an "
+        "optional top-k / top-p draw (gfx950)",
+        py::arg("logits"), py::arg("k"), py::arg("inv_temperature"),
+        py::arg("vocab_start") = 0, py::arg("u") = py::none(),
+        py::arg("top_k") = py::none(), py::arg("top_p") = py::none());
+  m.def("logits_topk_segment",
+        [](bool bf16) { return logits_topk_segment(bf16); },
+        "columns per segment of logits_topk for bf16 (else fp32) logits");
   m.def("attn_fwd", &attn_fwd, "flash attention fwd (gfx950 MFMA)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
         py::arg("scale"), py::arg("alibi") = py::none(),

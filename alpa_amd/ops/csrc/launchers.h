@@ -139,6 +139,31 @@ hipError_t launch_ce_bwd(const float* dloss, const void* logits,
                          void* dlogits, int64_t N, int64_t V,
                          int64_t vocab_start, hipStream_t stream);
 
+// ---- logits_sample.hip ----
+// columns per segment of the partial kernel: a function of the dtype alone
+int logits_topk_segment(int bf16);
+// logits [B, V] bf16 or fp32 with 16-byte-aligned rows row_stride elements
+// apart, y = float(x) * inv_t[b]; 1 <= k <= min(V, 128), 1 <= B <= 65535.
+// With nseg = ceil(V / segment): workspace stats [B, nseg, 2] fp32 and
+// cand_val (fp32) / cand_col (int32) [B, nseg, k].  Writes vals [B, k] (y,
+// descending, equal y by lower column), idx [B, k] = column + vocab_start,
+// m [B] = max y and s [B] = sum exp(y - m) (0 if m = -inf; both NaN if the
+// row holds a NaN).  u null: no draw.  Else u, top_p fp32 [B], top_k int32
+// [B] and token [B]: over the first n = (0 < top_k <= k ? top_k : k)
+// candidates, p_j = exp(y_j - y_0) summed in ascending j; candidate j is
+// kept iff j == 0 or the sum before it is below top_p * total; the token is
+// the first kept j whose sum through j exceeds u * (kept sum), else the last
+// kept; candidate 0 if y_0 is -inf or NaN
+hipError_t launch_logits_topk(const void* logits, int bf16,
+                              int64_t row_stride, const float* inv_t,
+                              int64_t B, int64_t V, int k,
+                              int64_t vocab_start, float* stats,
+                              float* cand_val, int* cand_col, float* vals,
+                              int64_t* idx, float* m, float* s,
+                              const float* u, const int* top_k,
+                              const float* top_p, int64_t* token,
+                              hipStream_t stream);
+
 // ---- attention.hip ----
 // strides: q(3) k(3) v(3) o(3), each (batch, head, seq) in elements
 hipError_t launch_attn_fwd(const void* q, const void* k, const void* v,

@@ -440,6 +440,57 @@ def softmax_cross_entropy_shard_bwd(dloss: torch.Tensor, logits: torch.Tensor,
     return (p * _up(dloss).unsqueeze(-1)).to(logits.dtype)
 
 
+def logits_topk(logits: torch.Tensor, k: int, inv_temperature=None,
+                vocab_start: int = 0):
+    """Top-k of y = float(logits) * inv_temperature[b] (one fp32 multiply)
+    with the statistics of a softmax over the row: (vals [B, k] fp32 sorted
+    descending, equal y by lower column; idx [B, k] int64 = column +
+    vocab_start; m [B] = max y; s [B] = sum exp(y - m), summed in fp64, 0
+    for a row of -inf only).  k is clamped to V.  A NaN in a row makes its
+    m and s NaN."""
+    B, V = logits.shape
+    y = logits.float()
+    if inv_temperature is not None:
+        y = y * inv_temperature.float().reshape(B, 1)
+    # a stable sort keeps equal values in column order
+    vals, idx = torch.sort(y, dim=-1, descending=True, stable=True)
+    k = min(int(k), V)
+    m = y.max(dim=-1).values
+    shift = torch.where(m == -math.inf, torch.zeros_like(m), m).double()
+    s = torch.exp(y.double() - shift.unsqueeze(-1)).sum(dim=-1)
+    return (vals[:, :k].contiguous(), idx[:, :k] + int(vocab_start), m,
+            s.float())
+
+
+def sample_logits(logits: torch.Tensor, u: torch.Tensor,
+                  inv_temperature: torch.Tensor, top_k: torch.Tensor,
+                  top_p: torch.Tensor, k: int = 64) -> torch.Tensor:
+    """One token per row by temperature / top-k / top-p sampling with an
+    inverse-CDF draw, every parameter per row ([B] tensors).  Over the first
+    n = (top_k if 0 < top_k <= k else k) entries of logits_topk(logits, k,
+    inv_temperature): p_j = exp(y_j - y_0), e_j = sum of p_i for i < j, T
+    their total; candidate j is kept iff j == 0 or e_j < top_p * T; T' is
+    the kept sum; the token is the first kept j with e_j + p_j > u * T',
+    else the last kept one.  A row whose y_0 is -inf or NaN gives candidate
+    0.  Arithmetic after y in fp64."""
+    vals, idx, _, _ = logits_topk(logits, k, inv_temperature)
+    kk = vals.shape[1]
+    j = torch.arange(kk, device=vals.device).unsqueeze(0)
+    tk = top_k.long().reshape(-1, 1)
+    n = torch.where((tk > 0) & (tk <= kk), tk, torch.full_like(tk, kk))
+    y = vals.double()
+    p = torch.where(j < n, torch.exp(y - y[:, :1]), torch.zeros_like(y))
+    e = p.cumsum(dim=-1) - p
+    T = p.sum(dim=-1, keepdim=True)
+    keep = (j < n) & ((j == 0) | (e < top_p.double().reshape(-1, 1) * T))
+    kept_sum = (p * keep).sum(dim=-1, keepdim=True)
+    hit = keep & (e + p > u.double().reshape(-1, 1) * kept_sum)
+    pick = torch.where(hit.any(dim=-1), hit.int().argmax(dim=-1),
+                       keep.sum(dim=-1) - 1)
+    pick = torch.where(vals[:, 0] > -math.inf, pick, torch.zeros_like(pick))
+    return idx.gather(1, pick.unsqueeze(1))[:, 0]
+
+
 def adamw_step(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float,
                beta1: float, beta2: float, eps: float, weight_decay: float,
                grad_scale: float = 1.0, grad_sumsq=None,

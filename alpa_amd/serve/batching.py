@@ -26,6 +26,11 @@ class GenRequest:
     eos_token: Optional[int] = None
     output: List[int] = field(default_factory=list)
     done: bool = False
+    # per-request sampling (ops.sample_logits; top_k 0: the 64 likeliest)
+    do_sample: bool = False
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
 
 
 def _SlotCacheView(cache, slot: int):
@@ -37,13 +42,22 @@ def _SlotCacheView(cache, slot: int):
 class ContinuousBatcher:
     """submit() requests, call step() in a loop (or run_all()); each step
     decodes one token for EVERY active slot and admits pending requests
-    into freed slots."""
+    into freed slots.  Requests carry their own sampling settings: they
+    sit in per-slot device tensors written at admission, and a tick with a
+    sampling request picks every slot's token in one ops.sample_logits
+    call (greedy slots as top_k = 1), its uniforms drawn from
+    `generator`; a tick without one is the greedy argmax."""
 
-    def __init__(self, model, max_batch: int):
+    def __init__(self, model, max_batch: int,
+                 generator: Optional[torch.Generator] = None):
         self.model = model
         self.B = max_batch
+        self.generator = generator
         self.cache = model.new_cache(max_batch)
         dev = self.cache.k[0].device
+        self.inv_t = torch.ones(max_batch, dtype=torch.float32, device=dev)
+        self.top_k = torch.ones(max_batch, dtype=torch.int32, device=dev)
+        self.top_p = torch.ones(max_batch, dtype=torch.float32, device=dev)
         self.lens = torch.zeros(max_batch, dtype=torch.long, device=dev)
         self.cur = torch.zeros(max_batch, 1, dtype=torch.long, device=dev)
         self.slots: List[Optional[GenRequest]] = [None] * max_batch
@@ -52,7 +66,39 @@ class ContinuousBatcher:
         self.max_len = self.cache.k[0].shape[2]
 
     def submit(self, req: GenRequest):
+        if req.do_sample:
+            mesh = getattr(self.model, "mesh", None)
+            assert mesh is None or mesh.axis_size(self.model.axis) == 1, \
+                "per-request sampling reads the whole vocab: tp == 1 only"
+            assert req.top_k <= 128, "top_k above 128 is not served"
         self.pending.append(req)
+
+    def _set_sampling(self, s: int, req: GenRequest):
+        """Slot s's sampling parameters; a greedy request is top_k = 1."""
+        if req.do_sample:
+            self.inv_t[s] = 1.0 / max(req.temperature, 1e-6)
+            # a fixed default, so a request's candidates never depend on
+            # its neighbours' settings
+            self.top_k[s] = req.top_k if req.top_k > 0 else 64
+            self.top_p[s] = req.top_p
+        else:
+            self.inv_t[s], self.top_k[s], self.top_p[s] = 1.0, 1, 1.0
+
+    def _pick(self, logits: torch.Tensor, slots: List[int]) -> torch.Tensor:
+        """The next token of each row of logits, row i belonging to
+        slots[i] (free slots ride along and are ignored)."""
+        reqs = [self.slots[s] for s in slots]
+        if not any(r is not None and r.do_sample for r in reqs):
+            return self.model.greedy_token(logits)
+        from .. import ops
+        sel = slice(None) if len(slots) == self.B else \
+            torch.tensor(slots, device=self.device)
+        dev = self.generator.device if self.generator is not None \
+            else self.device
+        u = torch.rand(len(slots), generator=self.generator, device=dev)
+        k = max([64] + [r.top_k for r in reqs if r is not None])
+        return ops.sample_logits(logits, u, self.inv_t[sel], self.top_k[sel],
+                                 self.top_p[sel], k=k)
 
     @property
     def num_active(self) -> int:
@@ -128,9 +174,11 @@ class ContinuousBatcher:
         view = self.cache.slots(s0, n)
         with torch.no_grad():
             logits = self.model.forward_prefill(ids, lens, view)
-        toks = self.model.greedy_token(logits)
-        for j, (s_, r) in enumerate(zip(slots, reqs)):
+        for s_, r in zip(slots, reqs):
             self.slots[s_] = r
+            self._set_sampling(s_, r)
+        toks = self._pick(logits, slots)
+        for j, (s_, r) in enumerate(zip(slots, reqs)):
             self.lens[s_] = int(lens[j])
             self.cur[s_, 0] = toks[j]
             r.output.append(int(toks[j]))
@@ -148,8 +196,9 @@ class ContinuousBatcher:
             view = _SlotCacheView(self.cache, s)
             with torch.no_grad():
                 logits = self.model.forward_step(ids, view)
-            tok = self.model.greedy_token(logits)
             self.slots[s] = req
+            self._set_sampling(s, req)
+            tok = self._pick(logits, [s])
             self.lens[s] = S0
             self.cur[s, 0] = tok[0]
             req.output.append(int(tok[0]))
@@ -175,7 +224,7 @@ class ContinuousBatcher:
         # free slots ride along with lens=0 (their rows are fully masked
         # by the kernel and their outputs ignored)
         logits = self.model.forward_decode(self.cur, self.cache, self.lens)
-        toks = self.model.greedy_token(logits)
+        toks = self._pick(logits, list(range(self.B)))
         finished = []
         for s in active:
             self.lens[s] += 1

@@ -17,8 +17,8 @@ __version__ = "0.1.0"
 #: the e4m3 KV cache; 11: attn_chunk and attn_chunk_fp8, query chunks over a
 #: KV cache; 12: 8-word AdamW descriptor rows with the twin fields, and
 #: adamw_check_twin; 13: qkv_cache_write, the fused qkv split, rotary and
-#: KV-cache write)
-MIN_HIP_OPS_ABI = 13
+#: KV-cache write; 14: logits_topk, the top-k log-prob and sampling kernels)
+MIN_HIP_OPS_ABI = 14
 
 
 def check_hip_ops_version() -> int:
